@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the phasing hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line. --dump-outputs DIR also writes what the last timed step
+computed (see dump_outputs). --full adds the side measurements, which cost time of their own: the CPU-oracle baselines, the
+emitted-haplotype count (a copy of the whole TSV into Python) and the chunked end-to-end leg.
 
 Metric (BASELINE.json): peptide-windows/s, `somatic`, 9-mer (27 nt), on the synthetic 20k-transcript
 whole exome (30x, ~5 variant sites per window). A "step" is one pass of the
@@ -20,9 +24,12 @@ The JSON line also carries
   roofline                 - the dominant unit's algorithmic bytes / its HIP-event time vs the 8 TB/s HBM peak (a unit = one kernel, or the
                              three window kernels that run concurrently, priced together over the phase's wall time)
   roofline_units, pass_hbm_frac, valu_issue - the same for every unit, for the whole pass, and the pass's VALU issue rate vs the chip's
+  end_to_end               - plan+pack+H2D, pass, D2H+consume wall times of rank 0 and the in-memory end-to-end rate
+and, with --full,
   cpu_baseline             - the CPU oracle (single thread, like the reference) on a bounded sample of the workload
   cpu_baseline_all_cores   - the same oracle with the sample's genes sharded over all host cores
-  end_to_end               - plan+pack+H2D, pass, D2H+consume wall times of rank 0 and the in-memory end-to-end rate
+  end_to_end.chunked       - the same end to end in overlapped gene chunks
+  replay.emitted_haplotypes - TSV rows (without it roofline.compulsory_bytes counts the hashed ids in their place)
 """
 import argparse
 import json
@@ -84,6 +91,46 @@ def cpu_baseline(cfg_name, sample_transcripts, threads=1):
     }
 
 
+DUMP_STREAMS = ("fasta", "normal_fasta", "tsv")   # mp_results_gene_offsets order
+DUMP_SEED = 20201
+DUMP_SAMPLE_GENES = 64        # genes of the seeded sample
+DUMP_SAMPLE_BYTES = 16384     # leading bytes of each sampled gene's part of a stream
+
+
+def dump_outputs(res, out_dir, prefix="", threads=1):
+    """What the timed path computed in its last step, as its caller receives it (the window count and the FASTA / normal FASTA / TSV
+    streams of the batch), written as <out_dir>/<prefix><name>.npy so that two builds can be compared output for output:
+      windows                      the consumer's window count (float64)
+      <stream>_gene_offsets        byte offset of every gene's part of the stream, and its end (float64, exact)
+      <stream>_crc32               CRC-32 of the stream's pieces between those offsets - the part before the first gene (the TSV
+                                   header), every gene's part, the rest - so the whole stream, compactly (float64, exact)
+      sample_genes                 DUMP_SAMPLE_GENES gene ordinals drawn with DUMP_SEED (float64)
+      <stream>_sample              the first DUMP_SAMPLE_BYTES bytes of each sampled gene's part, concatenated (float32)
+    For config C that is under 2 MB of offsets and checksums plus at most 3 x 4 MB of sampled bytes."""
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"windows": np.array([res.windows], dtype=np.float64)}
+    offsets = [res.gene_offsets(k) for k in range(len(DUMP_STREAMS))]
+    n_genes = max(0, max(len(o) for o in offsets) - 1)
+    sample = np.sort(np.random.default_rng(DUMP_SEED).permutation(n_genes)[:DUMP_SAMPLE_GENES])
+    arrays["sample_genes"] = sample.astype(np.float64)
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:   # (zlib.crc32 releases the GIL on large buffers)
+        for name, off in zip(DUMP_STREAMS, offsets):
+            data = memoryview(getattr(res, name))
+            cuts = [0] + list(off) + [len(data)]
+            parts = [data[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]   # head (the TSV header), the genes, the rest
+            arrays[name + "_gene_offsets"] = np.asarray(off, dtype=np.float64)
+            arrays[name + "_crc32"] = np.fromiter(pool.map(zlib.crc32, parts), dtype=np.float64, count=len(parts))
+            picked = b"".join(bytes(parts[1 + g][:DUMP_SAMPLE_BYTES]) for g in sample if g < len(off) - 1)
+            arrays[name + "_sample"] = np.frombuffer(picked, dtype=np.uint8).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    return arrays
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -91,11 +138,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C", choices=sorted(CONFIGS))
     ap.add_argument("--transcripts", type=int, default=0, help="override the transcript count (debugging)")
-    ap.add_argument("--cpu-sample", type=int, default=1000, help="transcripts in the single-thread CPU-baseline sample (0 = skip)")
-    ap.add_argument("--cpu-sample-all", type=int, default=4000, help="transcripts in the all-cores CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=1000, help="(--full) transcripts in the single-thread CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample-all", type=int, default=4000, help="(--full) transcripts in the all-cores CPU-baseline sample (0 = skip)")
     ap.add_argument("--no-consume", action="store_true", help="skip the end-to-end D2H + consumer leg")
-    ap.add_argument("--e2e-chunks", type=int, default=8, help="gene chunks of the overlapped end-to-end leg (end_to_end.chunked; <= 1 skips it)")
+    ap.add_argument("--e2e-chunks", type=int, default=8, help="(--full) gene chunks of the overlapped end-to-end leg (end_to_end.chunked; <= 1 skips it)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements: CPU-oracle baselines, emitted-haplotype count, chunked end to end")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64 / float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -104,13 +155,13 @@ def main():
         if world == 1 and args.gpus > 1:
             sys.exit("bench.py --gpus %d must be launched with torch.distributed.run (one rank per GPU)" % args.gpus)
 
-    import torch
-    dist = None
+    dist = None   # torch only for the ranks' process group: one GPU needs none (batch.run() returns once its streams have drained)
     # MP_BENCH_REHEARSE=1: run the N-rank code path on a box with ONE GPU (all ranks on device 0, gloo for the two reductions) -
     # a functional rehearsal of the launch contract, never a measurement (the line says so)
     rehearse = os.environ.get("MP_BENCH_REHEARSE") == "1"
     device_index = 0 if rehearse else local_rank
     if world > 1:
+        import torch
         import torch.distributed as dist
         torch.cuda.set_device(device_index)
         if rehearse:
@@ -148,8 +199,8 @@ def main():
     t_plan = time.perf_counter() - t0
 
     def sync_all():
-        torch.cuda.synchronize()
         if dist is not None:
+            torch.cuda.synchronize()
             dist.barrier()
             torch.cuda.synchronize()
 
@@ -176,14 +227,18 @@ def main():
     t0 = time.perf_counter()
     windows = None
     emitted = None
+    res = None
     if not args.no_consume:
         res = batch.results()
         windows = res.windows
     t_consume = time.perf_counter() - t0
-    if not args.no_consume:
+    if args.full and not args.no_consume:
         emitted = max(0, res.tsv.count(b"\n") - 1)   # TSV rows = emitted haplotypes (outside the timed leg: this copies the text into Python)
     if windows is None:
         windows = st.n_windows_planned
+    if args.dump_outputs:
+        dump_outputs(res if res is not None else batch.results(), args.dump_outputs,
+                     "" if world == 1 else "rank%d_" % rank, threads=min(16, n_cores))
 
     if dist is not None:
         red_dev = "cpu" if rehearse else "cuda"
@@ -285,7 +340,8 @@ def main():
                          "algorithmic_bytes_per_launch": int(dom_bytes), "avg_launch_ms": dom_ms, "rocprof_kernels": dom_kernels,
                          "compulsory_bytes": int(compulsory), "compulsory_frac": compulsory / t_pass / 1e9 / HBM_PEAK_GBS,
                          "compulsory_note": "whole pass, SURVEY 8(d) formula with this run's counts (%d reads, %d variants, %d steps, %d windows, %d haplotype groups, "
-                                            "%d emitted) over ms_per_step, against the 8 TB/s peak" % (st.n_reads, st.n_variants, st.n_steps, st.n_windows_device, st.n_groups, n_emit),
+                                            "%d %s) over ms_per_step, against the 8 TB/s peak" % (st.n_reads, st.n_variants, st.n_steps, st.n_windows_device, st.n_groups, n_emit,
+                                                                                                   "emitted" if emitted is not None else "hashed ids in place of the emitted count (--full counts it)"),
                          "pmc_over_compulsory": None if not pass_pmc else {
                              "raw": (pass_pmc["fetch_raw"] + pass_pmc["write"]) / compulsory, "with_fetch_x2": (2 * pass_pmc["fetch_raw"] + pass_pmc["write"]) / compulsory,
                              "write_bytes_per_pass": pass_pmc["write"], "fetch_bytes_raw_per_pass": pass_pmc["fetch_raw"], "source": traffic_src,
@@ -321,7 +377,7 @@ def main():
                            "note": "rank 0, in memory: decoded inputs -> plan + pack + H2D -> one pass -> D2H + consumer (FASTA / TSV text); "
                                    "windows_per_s is this rank's windows over the sum of the three legs; not part of `value`"},
         }
-        if world == 1 and not args.no_consume and args.e2e_chunks > 1:
+        if args.full and world == 1 and not args.no_consume and args.e2e_chunks > 1:
             # the same in-memory end to end in gene chunks whose legs overlap (microphaser_amd/pipeline.py phase_chunked): chunk i + 1 is
             # planned and uploaded on a second context of the GPU while chunk i is phased, downloaded and consumed
             try:
@@ -348,12 +404,12 @@ def main():
             out["ranks"] = rank_info
         if rehearse:
             out["rehearsal"] = "all ranks on one GPU, gloo reductions: functional check of the N-rank path, not a measurement"
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             cb = cpu_baseline(args.config, args.cpu_sample)
             if cb:
                 out["cpu_baseline"] = cb
                 out["vs_cpu_baseline"] = value / cb["value"]
-        if world == 1 and args.cpu_sample_all > 0 and n_cores > 1:
+        if args.full and world == 1 and args.cpu_sample_all > 0 and n_cores > 1:
             cb = cpu_baseline(args.config, args.cpu_sample_all, threads=n_cores)
             if cb:
                 out["cpu_baseline_all_cores"] = cb

@@ -15,10 +15,10 @@ CASES = json.load(open(os.path.join(GOLDEN, "consumer", "cases.json")))
 
 
 def unpack(name, tmp_path):
-    """The committed dumps are gzip-compressed (records are mostly padding): unpack one into the test's directory."""
-    import gzip
+    """The committed dumps are xz-compressed (records are mostly padding): unpack one into the test's directory."""
+    import lzma
     path = str(tmp_path / (name + ".bin"))
-    with gzip.open(os.path.join(GOLDEN, "consumer", name + ".bin.gz"), "rb") as src, open(path, "wb") as dst:
+    with lzma.open(os.path.join(GOLDEN, "consumer", name + ".bin.xz"), "rb") as src, open(path, "wb") as dst:
         dst.write(src.read())
     return path
 
