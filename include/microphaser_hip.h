@@ -204,8 +204,14 @@ void mp_results_free(mp_results* r);
 /* `microphaser build_reference` (reference: peptides::build, src/peptides.rs:148-186 <- run_build, src/main.rs:146-169):
  * translate every 3-nt-step window of every record of a nucleotide FASTA (reverse-complemented when the id does not
  * end in 'F', stop codons -> 'X') and build the set of distinct peptides. Translation and de-duplication run on the
- * GPU. peptide_len <= 12. */
+ * GPU. 1 <= peptide_len <= 25.
+ *
+ * Peptide keys: key = sum_j ((aa_j - 'A') & 31) << 5 * (peptide_len - 1 - j), first residue most significant (keys of one length
+ * sort in string order). A key takes mp_key_words(peptide_len) uint64_t words: 1 for peptide_len <= 12, 2 for 13..25. A two-word
+ * key is an unsigned 128-bit little-endian integer, low word first (the bytes of unsigned __int128 / u128). Every key array of this
+ * ABI (mp_translate, mp_peptides_keys, mp_peptides_union) holds count * words words. */
 typedef struct mp_peptides mp_peptides;
+uint32_t mp_key_words(uint32_t peptide_len);   /* 1 or 2; 0 for a peptide length outside 1..25 */
 int mp_build_reference(mp_ctx* ctx, const char* fasta_path, uint32_t peptide_len, mp_peptides** out);
 int mp_build_reference_buffer(mp_ctx* ctx, const char* fasta_text, size_t len, uint32_t peptide_len, mp_peptides** out);   /* the FASTA's bytes */
 /* The same without the translated FASTA (mp_peptides_fasta is empty): the peptidome only - keys and binary -, what a pipeline that
@@ -214,22 +220,26 @@ int mp_peptidome_from_buffer(mp_ctx* ctx, const char* fasta_text, size_t len, ui
 const char* mp_peptides_fasta(const mp_peptides* p, size_t* len);     /* stdout of build_reference            */
 const char* mp_peptides_binary(const mp_peptides* p, size_t* len);    /* --output: bincode HashSet<Vec<u8>>   */
 const uint64_t* mp_peptides_keys(const mp_peptides* p, size_t* n);    /* sorted distinct keys (5 bits/residue): the unit
-                                                                         exchanged in the multi-GPU peptidome union */
+                                                                         exchanged in the multi-GPU peptidome union; *n = the
+                                                                         number of KEYS, the array holds *n * words words */
+uint32_t mp_peptides_key_words(const mp_peptides* p);                 /* words per key: 1 or 2                */
 uint64_t mp_peptides_count(const mp_peptides* p);                     /* translated windows                   */
 void mp_peptides_free(mp_peptides* p);
 /* to_protein (reference: src/peptides.rs:128-146) for n windows of 3 * peptide_len nucleotides laid out back to back in nt;
  * reverse[i] != 0: reverse complement first (ids that do not end in 'F', :161-164). aa gets n * peptide_len residues (stop = 'X'),
- * keys (may be NULL) the 5-bit-per-residue keys. Runs on the GPU. */
+ * keys (may be NULL) the n keys: n * mp_key_words(peptide_len) words. Runs on the GPU. */
 int mp_translate(mp_ctx* ctx, const uint8_t* nt, const uint8_t* reverse, uint64_t n, uint32_t peptide_len, uint8_t* aa, uint64_t* keys);
 /* The exchange step of a multi-GPU build_reference: the union of sorted distinct key arrays (one per rank, as
- * all-gathered) -> one peptidome with the same accessors (its FASTA stream is empty). Host-side merge of sorted runs; no GPU needed. */
+ * all-gathered) -> one peptidome with the same accessors (its FASTA stream is empty). counts[a] is the number of KEYS of array a, which
+ * holds counts[a] * mp_key_words(peptide_len) words (need not be 16-byte aligned); sorted and distinct in key order (for two-word keys:
+ * the high word first). Host-side merge of sorted runs; no GPU needed. */
 int mp_peptides_union(mp_ctx* ctx, const uint64_t* const* keys, const uint64_t* counts, uint32_t n_arrays, uint32_t peptide_len, mp_peptides** out);
 
 /* `microphaser filter` (reference: peptides::filter, src/peptides.rs:221-709 <- run_filtering, src/main.rs:170-214,
  * src/filter_cli.yaml): translate the mutant / normal windows of a `somatic` info.tsv, drop self-similar, repeated and
  * post-stop peptides, remove those present in the reference peptidome (bincode HashSet<Vec<u8>> from build_reference)
  * and annotate the rest with the maximum-likelihood frequency and the 95 % credible interval of their variant region.
- * Translation, peptidome membership and the per-region statistics run on the GPU. peptide_len <= 12.
+ * Translation, peptidome membership and the per-region statistics run on the GPU. 1 <= peptide_len <= 25.
  * mp_filter reads the two files; mp_filter_buffers takes their bytes (read in place); mp_filter_peptides takes the peptidome as the
  * handle build_reference / mp_peptides_union returned (its sorted keys go to the GPU as they are: no bincode round trip) and
  * filters at that peptidome's peptide length. */

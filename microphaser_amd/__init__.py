@@ -198,6 +198,8 @@ def lib():
         "mp_peptides_fasta": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
         "mp_peptides_binary": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
         "mp_peptides_keys": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
+        "mp_peptides_key_words": (u32, [vp]),
+        "mp_key_words": (u32, [u32]),
         "mp_peptides_count": (u64, [vp]),
         "mp_peptides_free": (None, [vp]),
         "mp_filter": (i32, [vp, cp, cp, u32, pp]),
@@ -229,7 +231,7 @@ C_ABI_SYMBOLS = [
     "mp_filtered_removed_fasta", "mp_filtered_count", "mp_filtered_free",
     "mp_synth_gene_costs", "mp_dataset_from_arrays", "mp_dataset_to_arrays", "mp_gene_batch_free", "mp_dataset_gene_costs",
     "mp_batch_create_genes", "mp_results_gene_offsets", "mp_translate", "mp_peptides_union", "mp_build_reference_buffer", "mp_peptidome_from_buffer",
-    "mp_batch_results_dump", "mp_batch_results_from_dump",
+    "mp_batch_results_dump", "mp_batch_results_from_dump", "mp_peptides_key_words", "mp_key_words",
 ]
 
 
@@ -327,20 +329,28 @@ class Context:
         return Dataset(self, h)
 
     def translate(self, nt, reverse, peptide_len):
-        """to_protein on the GPU for len(reverse) windows of 3 * peptide_len nucleotides: (amino acids bytes, list of keys)."""
+        """to_protein on the GPU for len(reverse) windows of 3 * peptide_len nucleotides: (amino acids bytes, list of keys as Python ints)."""
         n = len(reverse)
         assert len(nt) == n * 3 * peptide_len
+        w = max(1, lib().mp_key_words(peptide_len))   # (an invalid length is refused by mp_translate)
         aa = ctypes.create_string_buffer(max(1, n * peptide_len))
-        keys = (ctypes.c_uint64 * max(1, n))()
+        keys = (ctypes.c_uint64 * max(1, n * w))()
         self._check(lib().mp_translate(self._h, bytes(nt), bytes(bytearray(reverse)), n, peptide_len, ctypes.cast(aa, ctypes.c_void_p), ctypes.cast(keys, ctypes.c_void_p)))
-        return aa.raw[:n * peptide_len], list(keys)[:n]
+        return aa.raw[:n * peptide_len], _keys_to_ints(list(keys)[:n * w], w)
 
     def peptides_union(self, key_arrays, peptide_len):
-        """Union of sorted distinct key arrays (one per rank) -> Peptides (keys, binary)."""
+        """Union of sorted distinct key arrays (one per rank) -> Peptides (keys, binary). Arrays of two-word keys (peptide_len 13..25)
+        are (n, 2) uint64 with columns [lo, hi], as Peptides.keys_np holds them."""
         import numpy as np
+        w = lib().mp_key_words(peptide_len)
         arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in key_arrays]
+        for a in arrs:
+            if w == 2 and (a.ndim != 2 or a.shape[1] != 2) and a.size:
+                raise ValueError("peptide length %d takes two-word keys: (n, 2) uint64 arrays, columns [lo, hi]" % peptide_len)
+            if w == 1 and a.ndim != 1:
+                raise ValueError("peptide length %d takes one-word keys: 1-D uint64 arrays" % peptide_len)
         ptrs = (ctypes.c_void_p * max(1, len(arrs)))(*[a.ctypes.data if a.size else None for a in arrs])
-        counts = (ctypes.c_uint64 * max(1, len(arrs)))(*[a.size for a in arrs])
+        counts = (ctypes.c_uint64 * max(1, len(arrs)))(*[a.shape[0] if a.ndim else 0 for a in arrs])
         h = ctypes.c_void_p()
         self._check(lib().mp_peptides_union(self._h, ptrs, counts, len(arrs), peptide_len, ctypes.byref(h)))
         return Peptides(h, with_binary=False)     # .binary is encoded when somebody asks for it
@@ -370,8 +380,11 @@ class Peptides:
         self._binary = None
         p = L.mp_peptides_keys(h, ctypes.byref(n))
         import numpy as np
-        # the keys as a numpy array (a whole-exome peptidome holds ~10^7 of them); `.keys` gives the same as a Python list on demand
-        self.keys_np = np.frombuffer((ctypes.c_char * (8 * n.value)).from_address(p), dtype=np.uint64).copy() if n.value else np.zeros(0, dtype=np.uint64)
+        # the keys as a numpy array (a whole-exome peptidome holds ~10^7 of them): 1-D for one-word keys, (n, 2) with columns [lo, hi]
+        # for two-word keys (peptide length 13..25); `.keys` gives the same as a Python list of ints on demand
+        self.key_words = w = L.mp_peptides_key_words(h)
+        k = np.frombuffer((ctypes.c_char * (8 * w * n.value)).from_address(p), dtype=np.uint64).copy() if n.value else np.zeros(0, dtype=np.uint64)
+        self.keys_np = k if w == 1 else k.reshape(-1, 2)
         self._keys = None
         self.count = L.mp_peptides_count(h)
         if with_binary:
@@ -388,7 +401,7 @@ class Peptides:
     @property
     def keys(self):
         if self._keys is None:
-            self._keys = self.keys_np.tolist()
+            self._keys = _keys_to_ints(self.keys_np.reshape(-1).tolist(), self.key_words)
         return self._keys
 
     def close(self):
@@ -414,6 +427,11 @@ class Filtered:
             setattr(self, name, _bytes_at(p, n.value))
         self.rows, self.peptides, self.groups, self.kept, self.removed = (L.mp_filtered_count(h, k) for k in range(5))
         L.mp_filtered_free(h)
+
+
+def _keys_to_ints(words, w):
+    """Key words as the C ABI lays them out (w per key, low word first) -> Python ints."""
+    return words if w == 1 else [(hi << 64) | lo for lo, hi in zip(words[0::2], words[1::2])]
 
 
 def key_to_peptide(key, length):

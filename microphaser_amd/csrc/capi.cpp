@@ -422,7 +422,9 @@ const char* mp_peptides_binary(const mp_peptides* p, size_t* len) {
     if (len) *len = q->bin.size();
     return q->bin.data();
 }
-const uint64_t* mp_peptides_keys(const mp_peptides* p, size_t* n) { if (n) *n = p->res.keys.size(); return p->res.keys.data(); }
+const uint64_t* mp_peptides_keys(const mp_peptides* p, size_t* n) { if (n) *n = p->res.n_keys(); return p->res.keys.data(); }
+uint32_t mp_peptides_key_words(const mp_peptides* p) { return key_words(p->res.peptide_len); }
+uint32_t mp_key_words(uint32_t peptide_len) { return peptide_len >= 1 && peptide_len <= MAX_PEPTIDE_LEN ? key_words(peptide_len) : 0; }
 uint64_t mp_peptides_count(const mp_peptides* p) { return p->res.n_peptides; }
 void mp_peptides_free(mp_peptides* p) { delete p; }
 

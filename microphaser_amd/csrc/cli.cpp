@@ -44,7 +44,7 @@ int main(int argc, char** argv) {
     std::string sub = argv[1];
     if (sub == "build_reference") {
         // microphaser build_reference --reference peptides.fasta -l 9 --output peptides.bin > translated.fasta
-        // (reference: src/build_ref_cli.yaml:10-31, src/main.rs:146-169)
+        // (reference: src/build_ref_cli.yaml:10-31, src/main.rs:146-169); -l 1..25 (13..25: MHC class II, two-word peptide keys)
         std::string ref, outp;
         unsigned peptide_len = 9;
         int device = 0;
@@ -79,6 +79,7 @@ int main(int argc, char** argv) {
     if (sub == "filter") {
         // microphaser filter -t info.tsv -r reference.binary [-o info.filtered.tsv] [-s info.removed.tsv] [-p peptides.removed.fasta]
         //                    [-n normal.filtered.fa] [-l 9] > tumor.filtered.fa          (src/filter_cli.yaml, src/main.rs:170-214)
+        // -l 1..25, the length build_reference was run with
         std::string tsv, ref, tsvo = "info.filtered.tsv", simo = "info.removed.tsv", remp = "peptides.removed.fasta", normo = "normal.filtered.fa";
         unsigned peptide_len = 9;
         int device = 0;

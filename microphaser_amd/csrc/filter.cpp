@@ -296,7 +296,8 @@ typename V::value_type* to_device(const V& v, hipStream_t stream, std::vector<vo
 
 void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
                    uint32_t L, FilterResult& out) {
-    if (L == 0 || L > 12) throw Error("peptide length must be 1..12 for the device peptidome (5-bit residue keys in a u64)");
+    check_peptide_len(L);
+    const uint32_t w = key_words(L);
     out = FilterResult();
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -312,7 +313,7 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
     const size_t threads = host_threads();
 
     // ---- reference peptidome: bincode v1 HashSet<Vec<u8>> (deserialize_from(...).unwrap(), :242) -> keys of the length-L members;
-    //      or the sorted distinct keys themselves (a peptidome that never left the library)
+    //      or the sorted distinct keys themselves (a peptidome that never left the library). Keys of w words each (pep.hpp).
     std::vector<uint64_t> ref_keys;
     if (!reference_keys) {
         size_t p = 0;
@@ -332,11 +333,7 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
             if (l == L) {  // only a member of the same length can equal a tumor peptide
                 bool letters = true;
                 for (uint64_t k = 0; k < l; k++) { const char c = reference_binary[p + k]; letters &= c >= 'A' && c <= 'Z'; }
-                if (letters) {
-                    uint64_t key = 0;
-                    for (uint64_t k = 0; k < l; k++) key = (key << 5) | uint64_t((reference_binary[p + k] - 'A') & 31);   // = peptide_to_key
-                    ref_keys.push_back(key);
-                }
+                if (letters) push_key(ref_keys, peptide_to_key(reference_binary.data() + p, l), w);
             }
             p += l;
         }
@@ -398,14 +395,14 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
         uint64_t n_ref = 0;
         uint64_t* d_ref = nullptr;
         if (reference_keys) {
-            n_ref = reference_keys->size();
+            n_ref = reference_keys->size() / w;
             if (n_ref) d_ref = to_device(*reference_keys, stream, owned);
         } else if (!ref_keys.empty()) {
             uint64_t* d_in = to_device(ref_keys, stream, owned);
             void *d_tmp = nullptr, *d_out = nullptr;
             HIP_OK(hipMalloc(&d_tmp, ref_keys.size() * 8)); owned.push_back(d_tmp);
             HIP_OK(hipMalloc(&d_out, ref_keys.size() * 8)); owned.push_back(d_out);
-            n_ref = device_sort_unique(d_in, static_cast<uint64_t*>(d_tmp), static_cast<uint64_t*>(d_out), ref_keys.size(), 5 * L, stream);
+            n_ref = device_sort_unique(d_in, static_cast<uint64_t*>(d_tmp), static_cast<uint64_t*>(d_out), ref_keys.size() / w, L, stream);
             d_ref = static_cast<uint64_t*>(d_out);
         }
         // ---- K5

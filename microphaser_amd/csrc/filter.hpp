@@ -22,7 +22,7 @@ struct FilterResult {
 };
 
 // reference_binary: bytes of the bincode HashSet<Vec<u8>> written by build_reference - or, with reference_keys != nullptr, the
-// peptidome as sorted distinct keys of peptide_len residues (PeptideResult::keys; reference_binary is then not read);
+// peptidome as sorted distinct keys of peptide_len residues, key_words(peptide_len) words each (PeptideResult::keys; reference_binary is then not read);
 // tsv_text: info.tsv of `somatic`. Both buffers are read in place and must stay valid for the call.
 void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
                    uint32_t peptide_len, FilterResult& out);

@@ -1,6 +1,7 @@
 // K5 / K6: the device side of `microphaser filter` (reference: src/peptides.rs:188-709).
 //   K5 translates the mutant / normal nucleotide windows of the neopeptide table and tests every peptide of the tumor
-//      protein against the reference peptidome (sorted 5-bit keys, binary search) - byte / integer work.
+//      protein against the reference peptidome (sorted 5-bit keys, binary search; u64 keys for L <= 12, 16-byte keys for
+//      13 <= L <= 25, pep.hpp) - byte / integer work.
 //   K6 evaluates, per group of records that share a variant region, the binomial likelihood grid, its Simpson integral
 //      in log space and the iterative 95 % credible-interval search - f64, transcendental-bound, one thread per group.
 //      Restates statrs 0.15 Binomial::pmf / ln_binomial / ln_gamma and bio 0.34 LogProb::{ln_simpsons_integrate_exp,
@@ -8,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_filter.hpp"
+#include "pep.hpp"
 
 namespace mp {
 
@@ -23,10 +25,12 @@ __device__ __forceinline__ int base2f(uint8_t c, bool complement) {
     return complement ? 3 - b : b;
 }
 
+// K = uint64_t (L <= 12) or unsigned __int128 (13 <= L <= 25): the rolling key lives in registers, one K-sized load per probe
+template <class K>
 __global__ __launch_bounds__(256) void k5_translate_records(const uint8_t* __restrict__ nt, const uint64_t* __restrict__ nt_off,
                                                             const uint32_t* __restrict__ nt_len, const uint8_t* __restrict__ rev,
                                                             const uint64_t* __restrict__ aa_off, uint64_t n_seq, uint32_t L,
-                                                            const uint64_t* __restrict__ ref_keys, uint64_t n_ref, uint8_t* __restrict__ aa,
+                                                            const K* __restrict__ ref_keys, uint64_t n_ref, uint8_t* __restrict__ aa,
                                                             uint8_t* __restrict__ flags, uint32_t* __restrict__ err) {
     const uint64_t s = uint64_t(blockIdx.x) * 256 + threadIdx.x;
     if (s >= n_seq) return;
@@ -37,8 +41,10 @@ __global__ __launch_bounds__(256) void k5_translate_records(const uint8_t* __res
     const bool rc = rev[s] != 0;
     uint8_t* out = aa + aa_off[s];
     const uint32_t ncod = len > 2 ? (len - 2 + 2) / 3 : 0;   // i = 0, 3, ... while i < len - 2
-    const uint64_t kmask = L >= 12 ? ~0ull >> 4 : ((1ull << (5 * L)) - 1ull);
-    uint64_t key = 0;
+    K kmask;
+    if constexpr (sizeof(K) == 8) kmask = L >= 12 ? ~0ull >> 4 : ((1ull << (5 * L)) - 1ull);
+    else kmask = (K(1) << (5 * L)) - 1;   // 5L <= 125
+    K key = 0;
     uint32_t x_dist = 0xFFFFFFFFu;   // codons since the last 'X'
     bool bad = false;
     for (uint32_t j = 0; j < ncod; j++) {
@@ -48,14 +54,15 @@ __global__ __launch_bounds__(256) void k5_translate_records(const uint8_t* __res
         char a = '?';
         if ((b0 | b1 | b2) < 0) bad = true; else a = CODON_AA_F[16 * b0 + 4 * b1 + b2];
         out[j] = uint8_t(a);
-        key = ((key << 5) | uint64_t((a - 'A') & 31)) & kmask;
+        key = ((key << 5) | K((a - 'A') & 31)) & kmask;
         x_dist = a == 'X' ? 0u : (x_dist == 0xFFFFFFFFu ? x_dist : x_dist + 1);
         if (j + 1 >= L) {  // peptide i = j + 1 - L is complete
             uint8_t f = (x_dist != 0xFFFFFFFFu && x_dist < L) ? 1 : 0;
             uint64_t lo = 0, hi = n_ref;
             while (lo < hi) {
                 const uint64_t mid = (lo + hi) >> 1;
-                if (ref_keys[mid] < key) lo = mid + 1; else hi = mid;
+                const K r = ref_keys[mid];
+                if (r < key) lo = mid + 1; else hi = mid;
             }
             if (lo < n_ref && ref_keys[lo] == key) f |= 2;
             flags[aa_off[s] + (j + 1 - L)] = f;
@@ -69,8 +76,12 @@ void device_translate_records(const uint8_t* d_nt, const uint64_t* d_nt_off, con
                               uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err, hipStream_t stream) {
     if (!n_seq) return;
     dim3 grid(uint32_t((n_seq + 255) / 256)), block(256);
-    hipLaunchKernelGGL(k5_translate_records, grid, block, 0, stream, d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq, L, d_ref_keys, n_ref,
-                       d_aa, d_flags, d_err);
+    if (key_words(L) == 1)
+        hipLaunchKernelGGL(k5_translate_records<uint64_t>, grid, block, 0, stream, d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq, L,
+                           d_ref_keys, n_ref, d_aa, d_flags, d_err);
+    else
+        hipLaunchKernelGGL(k5_translate_records<unsigned __int128>, grid, block, 0, stream, d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq,
+                           L, reinterpret_cast<const unsigned __int128*>(d_ref_keys), n_ref, d_aa, d_flags, d_err);
     HIP_OK_(hipGetLastError());
 }
 

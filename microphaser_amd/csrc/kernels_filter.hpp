@@ -8,7 +8,8 @@ namespace mp {
 
 // K5: one thread per sequence (mutant / normal nucleotide window of a TSV row): to_protein (src/peptides.rs:128-146) into
 // aa[aa_off[s] ..], then for every peptide_len-mer of it a 5-bit key, a "contains X" flag and membership in the sorted
-// reference peptidome keys (binary search).  flags bit0 = has X, bit1 = member of the reference set.
+// reference peptidome keys (binary search; n_ref keys of key_words(L) u64 words each, pep.hpp - a two-word array 16-byte aligned).
+// flags bit0 = has X, bit1 = member of the reference set.
 void device_translate_records(const uint8_t* d_nt, const uint64_t* d_nt_off, const uint32_t* d_nt_len, const uint8_t* d_rev,
                               const uint64_t* d_aa_off, uint64_t n_seq, uint32_t L, const uint64_t* d_ref_keys, uint64_t n_ref,
                               uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err, hipStream_t stream);

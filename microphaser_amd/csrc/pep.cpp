@@ -15,27 +15,35 @@ namespace mp {
 [[noreturn]] void throw_hip(hipError_t e, const char* file, int line);
 #define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw_hip(e_, __FILE__, __LINE__); } while (0)
 
-std::string peptide_from_key(uint64_t key, uint32_t L) {
-    std::string s(L, 'A');
-    for (uint32_t j = 0; j < L; j++) s[L - 1 - j] = char('A' + ((key >> (5 * j)) & 31));
-    return s;
+void check_peptide_len(uint32_t L) {
+    if (L == 0 || L > MAX_PEPTIDE_LEN)
+        throw Error("peptide length must be 1..25 for the device peptidome (5-bit residue keys in one or two u64 words)");
 }
-uint64_t peptide_to_key(const std::string& pep) {
-    uint64_t k = 0;
-    for (char c : pep) k = (k << 5) | uint64_t((c - 'A') & 31);
+
+key128 peptide_to_key(const char* pep, size_t L) {
+    key128 k = 0;
+    for (size_t j = 0; j < L; j++) k = (k << 5) | key128((pep[j] - 'A') & 31);
     return k;
+}
+std::string peptide_from_key(key128 key, uint32_t L) {
+    std::string s(L, 'A');
+    for (uint32_t j = 0; j < L; j++) s[L - 1 - j] = char('A' + (uint32_t(key >> (5 * j)) & 31));
+    return s;
 }
 
 std::string PeptideResult::binary() const {
     std::string b;
     auto u64 = [&](uint64_t v) { for (int i = 0; i < 8; i++) b.push_back(char(v >> (8 * i))); };
-    u64(keys.size());
-    for (uint64_t k : keys) { u64(peptide_len); b += peptide_from_key(k, peptide_len); }
+    const uint32_t w = key_words(peptide_len);
+    const size_t n = n_keys();
+    u64(n);
+    for (size_t i = 0; i < n; i++) { u64(peptide_len); b += peptide_from_key(key_at(keys.data(), i, w), peptide_len); }
     return b;
 }
 
 void build_reference_device(int device, std::string_view fasta_text, uint32_t L, PeptideResult& out, bool want_fasta) {
-    if (L == 0 || L > 12) throw Error("peptide length must be 1..12 for the device peptidome (5-bit residue keys in a u64)");
+    check_peptide_len(L);
+    const uint32_t w = key_words(L);
     out = PeptideResult();
     out.peptide_len = L;
     // parse records (bio::io::fasta::Reader), lay out the windows: i = 0, 3, ... while i + 3L <= len  (:165-174)
@@ -145,7 +153,7 @@ void build_reference_device(int device, std::string_view fasta_text, uint32_t L,
     std::vector<uint8_t> aa(want_fasta ? n * L : 0);
     if (n) {
         HIP_OK(hipMalloc(&d_nt, nt.size() + 64)); HIP_OK(hipMalloc(&d_rev, n)); HIP_OK(hipMalloc(&d_aa, n * L));
-        HIP_OK(hipMalloc(&d_off, n * 8)); HIP_OK(hipMalloc(&d_keys, n * 8)); HIP_OK(hipMalloc(&d_tmp, n * 8)); HIP_OK(hipMalloc(&d_out, n * 8));
+        HIP_OK(hipMalloc(&d_off, n * 8)); HIP_OK(hipMalloc(&d_keys, n * w * 8)); HIP_OK(hipMalloc(&d_tmp, n * w * 8)); HIP_OK(hipMalloc(&d_out, n * w * 8));
         HIP_OK(hipMalloc(&d_err, 4));
         HIP_OK(hipMemcpyAsync(d_nt, nt.data(), nt.size(), hipMemcpyHostToDevice, stream));
         HIP_OK(hipMemcpyAsync(d_off, off.data(), n * 8, hipMemcpyHostToDevice, stream));
@@ -154,13 +162,13 @@ void build_reference_device(int device, std::string_view fasta_text, uint32_t L,
         HIP_OK(hipEventRecord(e0, stream));
         device_translate(d_nt, d_off, d_rev, n, L, d_aa, d_keys, d_err, stream);
         HIP_OK(hipEventRecord(e1, stream));
-        uint64_t nu = device_sort_unique(d_keys, d_tmp, d_out, n, 5 * L, stream);
+        uint64_t nu = device_sort_unique(d_keys, d_tmp, d_out, n, L, stream);
         HIP_OK(hipEventRecord(e2, stream));
         uint32_t err = 0;
-        out.keys.resize(nu);
+        out.keys.resize(nu * w);
         HIP_OK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, stream));
         if (want_fasta) HIP_OK(hipMemcpyAsync(aa.data(), d_aa, n * L, hipMemcpyDeviceToHost, stream));
-        if (nu) HIP_OK(hipMemcpyAsync(out.keys.data(), d_out, nu * 8, hipMemcpyDeviceToHost, stream));
+        if (nu) HIP_OK(hipMemcpyAsync(out.keys.data(), d_out, nu * w * 8, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
         HIP_OK(hipEventElapsedTime(&out.translate_ms, e0, e1));
         HIP_OK(hipEventElapsedTime(&out.dedup_ms, e1, e2));

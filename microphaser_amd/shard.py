@@ -5,7 +5,7 @@ genes, src/microphasing.rs:895-942, :1963-1979), so `somatic` / `normal` need no
 are dealt to the ranks by estimated cost (longest processing time first on CDS_nt x depth), every rank phases
 its own genes, and the output streams are merged back into GTF order - the reference's output order - from the per-gene byte
 offsets the library reports (mp_results_gene_offsets). The one real exchange step of the path is the peptidome union of
-`build_reference` (config E): sorted distinct u64 keys, all-gathered as tensors (RCCL over xGMI on GPUs, gloo on CPU) and
+`build_reference` (config E): sorted distinct peptide keys, all-gathered as tensors (RCCL over xGMI on GPUs, gloo on CPU) and
 merged by the library (mp_peptides_union).
 """
 import heapq
@@ -142,10 +142,11 @@ def gather_shards(local, dist=None, dst=0, device="cpu"):
 
 
 def allgather_keys(local_keys, dist=None, device="cpu"):
-    """The exchange step of the multi-GPU build_reference: every rank contributes its sorted distinct u64 peptide keys (a numpy
-    uint64 array or a torch int64 tensor - keys are < 2^60), every rank gets the list of all ranks' arrays (numpy uint64).
-    Variable-length all-gather = exchange the counts, pad to the maximum, one all_gather. Size at config E: the 20000-transcript
-    exome's peptidome is 70 M distinct 9-mers = 560 MB of keys (measured, profiles/r04o_config_e_20k_one_gpu.json); every distinct key
+    """The exchange step of the multi-GPU build_reference: every rank contributes its sorted distinct peptide keys (a numpy uint64
+    array or a torch int64 tensor holding the keys' bits: 1-D for one-word keys, (n, 2) with columns [lo, hi] for the two-word keys of
+    peptide lengths 13..25), every rank gets the list of all ranks' arrays (numpy uint64, same shape convention). Two-word keys
+    travel flattened and are reshaped on arrival. Variable-length all-gather = exchange the counts, pad to the maximum, one
+    all_gather. Size at config E: the 20000-transcript exome's peptidome is 70 M distinct 9-mers = 560 MB of keys (measured, profiles/r04o_config_e_20k_one_gpu.json); every distinct key
     is on at least one rank, so the ranks' arrays sum to >= 560 MB - >= 70 MB per rank at N = 8 - and every rank receives that sum.
     xGMI is point to point (7 links x ~153 GB/s per GPU): ~0.6 GB per rank is a few milliseconds for RCCL's all-gather, small
     beside the sort / unique that produced the keys. (Unmeasured on a multi-GPU node.)"""
@@ -155,8 +156,10 @@ def allgather_keys(local_keys, dist=None, device="cpu"):
         t = local_keys.to(device=device, dtype=torch.int64)
     else:
         t = torch.from_numpy(np.ascontiguousarray(local_keys, dtype=np.uint64).view(np.int64)).to(device)
+    shape = (-1, 2) if t.dim() == 2 else (-1,)
+    t = t.reshape(-1)
     if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
-        return [t.cpu().numpy().view(np.uint64)]
+        return [t.cpu().numpy().view(np.uint64).reshape(shape)]
     world = dist.get_world_size()
     n = torch.tensor([t.numel()], dtype=torch.int64, device=device)
     counts = [torch.zeros_like(n) for _ in range(world)]
@@ -166,7 +169,7 @@ def allgather_keys(local_keys, dist=None, device="cpu"):
     padded[: t.numel()] = t
     bufs = [torch.empty_like(padded) for _ in range(world)]
     dist.all_gather(bufs, padded)
-    return [b[: int(c.item())].cpu().numpy().view(np.uint64) for b, c in zip(bufs, counts)]
+    return [b[: int(c.item())].cpu().numpy().view(np.uint64).reshape(shape) for b, c in zip(bufs, counts)]
 
 
 def union_keys(ctx, local_keys, peptide_len, dist=None, device="cpu"):

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """BASELINE.json config E at full size on ONE GPU, stage by stage, with wall times (measurement tool):
 
-  normal (germline + somatic calls, every haplotype of every window) -> build_reference -l 9 -> somatic -> filter
+  normal (germline + somatic calls, every haplotype of every window) -> build_reference -l L -> somatic -> filter
 
 on the synthetic 20k-transcript exome (seed 2020, per-gene random streams). `normal` emits every window (~4x the text of `somatic`),
 so the exome is walked in gene chunks - exactly what the ranks of a multi-GPU run do with their shards (microphaser_amd/pipeline.py):
 per chunk normal -> FASTA -> build_reference -> sorted distinct keys; the chunks' key arrays are merged by mp_peptides_union; then
 `somatic` per chunk, shards merged by gene, and one `filter` over the merged TSV.
 
-  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--out gpurun_out/config_e.json]
+  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--peptide-len 9] [--out config_e.json]
+
+(--peptide-len L: windows of 3L nt in `normal` and `somatic`; 13..25 are the MHC class II lengths, with two-word peptide keys)
 """
 import argparse
 import json
@@ -24,11 +26,35 @@ import microphaser_amd as m
 from microphaser_amd.shard import merge_by_gene, shard_of
 
 
+def phased(ds, genes, window_len, mode, streams, skip_panics, skipped):
+    """(genes, RunStats, Results) of one batch of `genes`; with skip_panics, a batch that holds a gene the reference would panic on
+    (the oracle's --skip-panics) is phased gene by gene instead, that gene left out and recorded in `skipped`."""
+    try:
+        b = ds.batch_genes(genes, window_len=window_len, mode=mode)
+        st = b.run()
+        return [(genes, st, b.results(streams))]
+    except m.MicrophaserError as e:
+        if not (skip_panics and str(e).startswith("reference would panic")):
+            raise
+    out = []
+    for g in genes:
+        try:
+            b = ds.batch_genes([g], window_len=window_len, mode=mode)
+            st = b.run()
+            out.append(([g], st, b.results(streams)))
+        except m.MicrophaserError as e:
+            if not str(e).startswith("reference would panic"):
+                raise
+            skipped.append(g)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--transcripts", type=int, default=20000)
     ap.add_argument("--chunks", type=int, default=8)
     ap.add_argument("--peptide-len", type=int, default=9)
+    ap.add_argument("--skip-panics", action="store_true", help="leave out genes the reference would panic on (phased gene by gene)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     L = a.peptide_len
@@ -41,19 +67,21 @@ def main():
     cuts = [n * k // a.chunks for k in range(a.chunks + 1)]
     stats = dict(normal_windows=0, normal_fasta_bytes=0, normal_tsv_bytes=0, k2n_ms=0.0, k3_ms=0.0, k3b_ms=0.0, k1_ms=0.0, peptide_windows=0)
     key_arrays = []
+    skipped = {"normal": [], "somatic": []}
     t_normal = t_build = 0.0
     for c in range(a.chunks):
         genes = list(range(cuts[c], cuts[c + 1]))
         t0 = time.perf_counter()
-        b = ds.batch_genes(genes, window_len=3 * L, mode=m.MODE_NORMAL)
-        st = b.run()
-        res = b.results(m.STREAM_FASTA)       # build_reference reads the FASTA only
-        fa = res.fasta
-        stats["normal_windows"] += res.windows
+        parts = []
+        for _g, st, res in phased(ds, genes, 3 * L, m.MODE_NORMAL, m.STREAM_FASTA, a.skip_panics, skipped["normal"]):
+            parts.append(res.fasta)           # build_reference reads the FASTA only
+            stats["normal_windows"] += res.windows
+            stats["normal_tsv_bytes"] += res.size("tsv")
+            stats["k1_ms"] += st.k1_ms; stats["k2n_ms"] += st.k2seq_ms; stats["k3_ms"] += st.k3_ms; stats["k3b_ms"] += st.k3b_ms
+            res.close()
+        fa = parts[0] if len(parts) == 1 else b"".join(parts)
+        del parts
         stats["normal_fasta_bytes"] += len(fa)
-        stats["normal_tsv_bytes"] += res.size("tsv")
-        stats["k1_ms"] += st.k1_ms; stats["k2n_ms"] += st.k2seq_ms; stats["k3_ms"] += st.k3_ms; stats["k3b_ms"] += st.k3b_ms
-        res.close(); b.close()
         t_normal += time.perf_counter() - t0
         t0 = time.perf_counter()
         pep = ctx.peptidome(fa, L)            # keys only: nobody reads the translated FASTA in this pipeline
@@ -72,12 +100,11 @@ def main():
     som_windows = 0
     for c in range(a.chunks):
         genes = list(range(cuts[c], cuts[c + 1]))
-        b = ds.batch_genes(genes)
-        b.run()
-        r = b.results()
-        som_windows += r.windows
-        shards.append(shard_of(r, genes))
-        r.close(); b.close()
+        # windows of L codons: a 27-nt window holds no 15-mer
+        for gs, _st, r in phased(ds, genes, 3 * L, m.MODE_SOMATIC, m.STREAM_ALL, a.skip_panics, skipped["somatic"]):
+            som_windows += r.windows
+            shards.append(shard_of(r, gs))
+            r.close()
     merged = merge_by_gene(shards)
     del shards
     t["somatic_s"] = time.perf_counter() - t0
@@ -86,7 +113,7 @@ def main():
     t0 = time.perf_counter()
     f = ctx.filter(merged["tsv"], peptidome)        # the peptidome handle: its keys go to the GPU as they are
     t["filter_s"] = time.perf_counter() - t0
-    stats.update(filter_rows=f.rows, filter_kept=f.kept, filter_removed=f.removed, filter_groups=f.groups)
+    stats.update(filter_rows=f.rows, filter_kept=f.kept, filter_removed=f.removed, filter_groups=f.groups, skipped_genes=skipped)
     t["total_s"] = sum(v for k, v in t.items() if k != "generate_s")
     out = {"config": "E: normal + build_reference -l %d + somatic + filter, %d transcripts, %d gene chunks, one MI355X" % (L, a.transcripts, a.chunks),
            "wall_s": t, "stats": stats}
