@@ -84,8 +84,6 @@ struct Batch {
     PodVec<uint32_t> win_walk;           // bit per window: !WSF_SIMPLE (the general sequence walk: K3's list D)
     PodVec<uint32_t> win_simple;         // bit per window: WSF_SIMPLE && WSF_NOSTOP (the wave-per-window kernels route a window's groups to K3's list A / B or C by it)
     bool lane_on = false;                // K2a writes RowRecs and the lane kernel takes the eligible windows
-    bool lane_hash = false;              // ... including those of 9..16 columns (its hash-table form)
-    PodVec<WChunk> achunks;              // admission work items: (exon, first read, count <= 64)
     uint64_t n_adm = 0;                   // AdmEntry count (sum of ExonW::n_reads)
     PodVec<uint64_t> v_sombits;      // bit (variant index in the batch) set <=> somatic
     // transcripts whose speculative schedule ran into a failure: (index into tx, message); the plan stops before that step and the

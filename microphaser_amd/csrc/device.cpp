@@ -267,16 +267,6 @@ void DeviceContext::upload_impl(const Batch& b) {
     d_.wchunks_d = up(b.wchunks_d);
     d_.n_wchunks_d = uint32_t(b.wchunks_d.size());
     d_.rows_per_lane_w = b.rows_per_lane_w;
-    d_.achunks = up(b.achunks);
-    d_.n_achunks = uint32_t(b.achunks.size());
-    d_.k2a_flat = !std::getenv("MP_K2A_CHUNKS") && !b.exons_w.empty() && b.n_adm && b.n_adm < 0xFFFFFF00ull ? 1u : 0u;
-    d_.achunk_exons = nullptr;
-    if (!d_.k2a_flat) {   // the form with a wave per work item: every work item gets its exon's record beside it (one level of scalar loads
-        // instead of work item -> exon)
-        achunk_exons_.resize(b.achunks.size());
-        for (size_t k = 0; k < b.achunks.size(); k++) achunk_exons_[k] = b.exons_w[b.achunks[k].exon];
-        d_.achunk_exons = up(achunk_exons_);
-    }
     d_.step_ncols = up(b.step_ncols);
     d_.step_rlo = up(b.step_rlo);
     d_.step_rn = up(b.step_rn);
@@ -286,7 +276,6 @@ void DeviceContext::upload_impl(const Batch& b) {
     d_.n_adm = b.n_adm;
     d_.adm = static_cast<AdmEntry*>(dalloc(size_t(b.n_adm + 1) * sizeof(AdmEntry))); allocs_.push_back(d_.adm);
     d_.lane_on = b.lane_on ? 1u : 0u;
-    d_.lane_hash = b.lane_hash ? 1u : 0u;
     d_.winw = up(b.winw);
     d_.lane_win = up(b.lane_win);
     d_.win_trivial = up(b.win_trivial);
@@ -335,7 +324,7 @@ void DeviceContext::upload_impl(const Batch& b) {
     d_.win_blobs = nullptr;
     if (!b.normal && d_.n_wins) { d_.win_blobs = static_cast<WinBlob*>(dalloc(size_t(d_.n_wins) * sizeof(WinBlob))); allocs_.push_back(d_.win_blobs); }
     d_.exons_a = nullptr; d_.adm_map = nullptr;
-    if (d_.k2a_flat) {
+    if (b.n_adm) {
         d_.exons_a = static_cast<ExonA*>(dalloc(size_t(d_.n_exons_w) * sizeof(ExonA))); allocs_.push_back(d_.exons_a);
         d_.adm_map = static_cast<AdmMap*>(dalloc(size_t(b.n_adm) * sizeof(AdmMap))); allocs_.push_back(d_.adm_map);
     }
@@ -363,9 +352,8 @@ void DeviceContext::upload_impl(const Batch& b) {
     if (dbg)
         std::fprintf(stderr, "[mp]   upload: release of the previous batch %.1f ms, per-read table + input allocations %.1f ms, result arenas %.1f ms, copies %.1f ms\n",
                      ms_free, ms_inputs - ms_free, ms_alloc - ms_inputs, ms_since(t_up0) - ms_alloc);
-    achunk_exons_ = PodVec<ExonW>();
     launch_k0_read_variants(d_, stream_);
-    if (d_.k2a_flat) launch_k0_pack_admission(d_, stream_);
+    launch_k0_pack_admission(d_, stream_);
     if (d_.win_blobs) launch_k0_pack_windows(d_, stream_);   // (once per batch: K3's per-window records, plan.hpp WinBlob)
     HIP_OK(hipStreamSynchronize(stream_));
     pool_trim(false);   // idle blocks this batch had no use for go back to the device

@@ -77,7 +77,6 @@ class DeviceContext {
     void dfree(void* p);
     void pool_trim(bool all);
     std::vector<XferSeg> pending_up_;     // upload(): the arrays to copy once everything is allocated
-    PodVec<ExonW> achunk_exons_;          // upload(): staging of DeviceBatch::achunk_exons
     void xfer(const std::vector<XferSeg>& segs, bool to_device);
     void* dalloc(size_t bytes);
     template <class V> typename V::value_type* up(const V& v);

@@ -262,6 +262,13 @@ enum : uint32_t { ST_EMPTY = 0, ST_PENDING = 1, ST_ROW = 2, ST_MASK = 3, RF_BAD 
 
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ uint32_t lanes_below(uint64_t mask, uint32_t lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
+// `want` slots for the whole wave (a workgroup of one wave) from an allocator's cursor: lane 0 claims them, every lane gets the first one
+__device__ __forceinline__ uint64_t wave_claim(unsigned long long* cur, unsigned long long want, uint64_t part_lo) {
+    unsigned long long base = 0;
+    if (threadIdx.x == 0) base = atomicAdd(cur, want);
+    const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
+    return part_lo + ((uint64_t(bhi) << 32) | blo);
+}
 
 constexpr uint32_t REC_CHUNK = 128;     // HapRec slots per allocation (>= 64: one emit call)
 
@@ -620,10 +627,7 @@ __global__ __launch_bounds__(64) void k2_window_replay(DeviceBatch d) {
                 nvalid += has_zero ? 0u : 1u;
                 uint32_t werr = sticky_err;
                 if (chunk_pos + nvalid > chunk_end) {
-                    unsigned long long base = 0;
-                    if (lane == 0) base = atomicAdd(gcur, (unsigned long long)GROUP_CHUNK);
-                    uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                    chunk_pos = gpart_lo + ((uint64_t(bhi) << 32) | blo);
+                    chunk_pos = wave_claim(gcur, GROUP_CHUNK, gpart_lo);
                     chunk_end = chunk_pos + GROUP_CHUNK;
                 }
                 const bool can_write = chunk_end <= gpart_hi && nvalid <= GROUP_CHUNK;
@@ -639,10 +643,7 @@ __global__ __launch_bounds__(64) void k2_window_replay(DeviceBatch d) {
                     const uint64_t nm = __ballot(need);
                     const uint32_t nneed = __popcll(nm);
                     if (nneed && rec_pos + nneed > rec_end) {
-                        unsigned long long base = 0;
-                        if (lane == 0) base = atomicAdd(rcur, (unsigned long long)REC_CHUNK);
-                        uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                        rec_pos = rpart_lo + ((uint64_t(bhi) << 32) | blo);
+                        rec_pos = wave_claim(rcur, REC_CHUNK, rpart_lo);
                         rec_end = rec_pos + REC_CHUNK;
                     }
                     uint32_t rec = 0xFFFFFFFFu;
@@ -800,108 +801,42 @@ __device__ __forceinline__ uint64_t mask_extract(const uint64_t (&m)[W], uint32_
     const uint32_t nsh = base - flo;
     return nsh < 64 ? m[0] << nsh : 0ull;
 }
-
-template <int W>
-__global__ __launch_bounds__(64) void k2a_admission(DeviceBatch d) {
-    const WChunk A = d.achunks[blockIdx.x];   // one wave per 64 candidate reads of an exon: step_first = first read, n_steps = count
-    const ExonW e = d.achunk_exons[blockIdx.x];   // (= exons_w[A.exon], stored beside the work item: both loads go out together)
-    const bool is_rev = e.strand != 0;
-    const uint32_t rbase = e.rbase + e.read_lo;
-    const uint32_t sso0 = e.sso0, sso1 = e.sso1;
-    for (uint32_t k = A.step_first + threadIdx.x; k < A.step_first + A.n_steps; k += 64) {
-        const uint32_t gi = rbase + k;
-        const uint32_t start = d.r_pos[gi], end = d.r_end[gi], rvl = d.r_varlo[gi];
-        uint64_t dirty[W], sup[W];   // dirty: low quality, or support of a start-loss variant
+// somatic flags of the nc (1..64) columns from batch variant index gv on, in haplotype bit order ('+': the newest column, the highest
+// position, is bit 0)
+__device__ __forceinline__ uint64_t somatic_mask(const uint64_t* v_sombits, uint64_t gv, uint32_t nc, bool is_rev) {
+    const uint64_t x0 = v_sombits[gv >> 6], x1 = v_sombits[(gv >> 6) + 1];
+    const uint32_t sh = uint32_t(gv & 63);
+    uint64_t bits = (sh ? ((x0 >> sh) | (x1 << (64 - sh))) : x0) & (~0ull >> (64 - nc));
+    if (!is_rev) bits = __brevll(bits) >> (64 - nc);
+    return bits;
+}
+// k2w_window_rows / _multi: lane l < nb fetches step si0 + l - w[0] sso, w[2] col_hi, w[3] window, w[4] / w[5] the packed Step words (w[k]
+// = dword k of the Step; w[1] is not needed), w[6] step_rlo, w[7] step_rn | ncols << 16, w[8] / w[9] the window's somatic columns; returns
+// the lanes whose step prints a window that is not the lane kernel's (plan.cpp lane_window)
+__device__ __forceinline__ uint64_t fetch_steps(const DeviceBatch& d, const ExonW& e, bool is_rev, uint32_t si0, uint32_t nb, uint32_t (&w)[10]) {
+    const uint32_t lane = threadIdx.x;
 #pragma unroll
-        for (int w = 0; w < W; w++) {
-            sup[w] = d.r_sup[uint64_t(gi) * W + w];
-            dirty[w] = d.r_lq[uint64_t(gi) * W + w] | (sup[w] & bit_range(e.sl_f_lo, e.sl_f_hi, rvl + 64u * w));
-        }
-        AdmEntry out;
-        out.ord = 0xFFFFFFFFu;
-        out.seen_lo = 0;
-        auto try_step = [&](uint32_t si) -> bool {   // push_read at step si (after shrink_left, before extend_right)
-            // everything the decision needs is fetched in ONE round of loads and the decision itself is branch-free: with an early
-            // return after the window test the compiler fetches the column fields only afterwards - a second dependent round trip
-            const uint32_t* sp = reinterpret_cast<const uint32_t*>(d.steps + si);
-            const uint32_t s_sso = sp[0], s_col_hi = sp[2], s_w4 = sp[4], s_w5 = sp[5];   // [4]: cand_n | wlen << 16 | n_del << 24; [5]: n_add | ...
-            const uint32_t nc = d.step_ncols[si];
-            const uint32_t s_wlen = (s_w4 >> 16) & 0xFFu, s_nadd = s_w5 & 0xFFu;
-            const uint32_t tlo = s_col_hi - nc, thi = s_col_hi - s_nadd;
+    for (int k = 0; k < 10; k++) w[k] = 0;
+    if (lane < nb) {
+        const uint32_t si = si0 + lane;
+        const uint32_t* sp = reinterpret_cast<const uint32_t*>(d.steps + si);
+        w[0] = sp[0]; w[2] = sp[2]; w[3] = sp[3]; w[4] = sp[4]; w[5] = sp[5];
+        w[6] = d.step_rlo[si];
+        const uint32_t nc = d.step_ncols[si];
+        w[7] = uint32_t(d.step_rn[si]) | (nc << 16);
+        if (((w[5] >> 8) & SF_PRINT) && nc) {
             uint32_t flo, fhi;
-            tr_to_f(e, is_rev, tlo, thi, flo, fhi);
-            const bool encloses = !(end < s_sso + s_wlen) & !(start > s_sso);
-            const bool clean = !mask_hits<W>(dirty, flo, fhi, rvl);
-            const bool ok = encloses & clean;
-            out.ord = ok ? si : out.ord;
-            out.seen_lo = ok ? tlo : out.seen_lo;
-            return ok;
-        };
-        if (!is_rev) {
-            if (start >= e.first_key_lo && start <= sso0) {
-                try_step(e.step_off);                   // the first window's candidate range (:1229-1240)
-            } else if (start > sso0 && e.n_steps > 1 && start >= sso1) {
-                // afterwards only the reads that start exactly at sso (:1241-1248); steps 1.. advance by one nt each
-                uint32_t t = 1 + (start - sso1);
-                if (t < e.unit_steps) {
-                    try_step(e.step_off + t);            // sso(t) == start by the exon's arithmetic (plan.hpp ExonW::unit_steps)
-                } else if (t < e.n_steps) {
-                    uint32_t s_t = d.steps[e.step_off + t].sso;
-                    while (s_t > start && t > 1) s_t = d.steps[e.step_off + --t].sso;            // (never taken for unit steps)
-                    while (s_t < start && t + 1 < e.n_steps) s_t = d.steps[e.step_off + ++t].sso;
-                    if (s_t == start) try_step(e.step_off + t);
-                }
-            }
-        } else {
-            // candidate while sso - R <= start <= sso; sso never increases along the exon (one nt per step, repeats at the end)
-            const uint32_t top = start + e.range;
-            uint32_t t = sso0 > top ? sso0 - top : 0;   // first step with sso <= start + R if every step moved by one
-            if (t >= e.unit_steps) {                    // beyond the arithmetic stretch: look at the steps
-                if (t >= e.n_steps) t = e.n_steps - 1;
-                while (t > 0 && d.steps[e.step_off + t - 1].sso <= top) t--;
-                while (t < e.n_steps && d.steps[e.step_off + t].sso > top) t++;
-            }
-            for (; t < e.n_steps; t++) {
-                const uint32_t s_t = t < e.unit_steps ? sso0 - t : d.steps[e.step_off + t].sso;
-                if (s_t < start) break;
-                if (try_step(e.step_off + t)) break;
-            }
-        }
-        if (e.consumers & EW_WAVE) d.adm[uint64_t(e.adm_off) + k] = out;   // (only where a wave-per-window kernel will read it: 145 windows at config C)
-        if constexpr (W == 1) {
-            if (d.lane_on && (e.consumers & EW_LANE)) {   // the same facts flattened for the lane-per-window kernel (plan.hpp RowRecA)
-                uint32_t bad_from = 0xFFFFFFFFu;
-                if (out.ord != 0xFFFFFFFFu) {
-                    const uint64_t dm = dirty[0];
-                    if (!is_rev) {   // transcription order = forward index: the first dirty column at or after the oldest one seen
-                        const uint32_t from = max(out.seen_lo, rvl), sh = from - rvl;
-                        const uint64_t m = sh < 64 ? dm >> sh : 0ull;
-                        if (m) bad_from = from + uint32_t(__builtin_ctzll(m));
-                    } else {         // transcription order descends in forward index: the highest dirty column at or below the oldest one seen
-                        const uint32_t f_hi = e.f0 - (out.seen_lo - e.tr0);
-                        if (f_hi >= rvl) {
-                            const uint32_t rel = f_hi - rvl;
-                            const uint64_t m = rel >= 63 ? dm : (dm & ((2ull << rel) - 1ull));
-                            if (m) bad_from = e.tr0 + (e.f0 - (rvl + 63u - uint32_t(__builtin_clzll(m))));
-                        }
-                    }
-                }
-                RowRecA a;
-                a.key = is_rev ? ~start : end;
-                a.ord = out.ord;
-                a.bad_from = bad_from;
-                a.rvl = rvl;
-                d.rr_a[uint64_t(e.adm_off) + k] = a;
-                d.rr_sup[uint64_t(e.adm_off) + k] = sup[0];
-            }
+            tr_to_f(e, is_rev, w[2] - nc, w[2], flo, fhi);
+            const uint64_t bits = somatic_mask(d.v_sombits, uint64_t(e.vbase) + flo, nc, is_rev);
+            w[8] = uint32_t(bits); w[9] = uint32_t(bits >> 32);
         }
     }
+    return __ballot(lane < nb && ((w[5] >> 8) & SF_PRINT) && !k2l_takes(d.lane_on != 0, w[7] >> 16, w[7] & 0xFFFF));
 }
 
-// The flat form: a lane per admission-table entry (exon, read), whatever exon it belongs to - the chunk form above leaves a third of its
-// lanes empty (60 candidate reads per exon on average) and every wave has ONE chain of dependent loads in flight; here a lane holds
-// ITEMS entries and the loads of each level - entry -> exon fields + read fields -> the first step to try - go out for all of them
-// before anything is used. Same decisions, same outputs (the table index IS the entry).
+// K2a: a lane per admission-table entry (exon, read), whatever exon it belongs to - a wave per <= 64 reads of ONE exon left a third of its
+// lanes empty (60 candidate reads per exon on average). The loads of each level - entry -> exon fields + read fields -> the first step
+// to try - go out before anything is used. The table index IS the entry.
 #if MP_IN_PART(0)
 __global__ __launch_bounds__(256) void k0_pack_admission(DeviceBatch d) {
     const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
@@ -928,14 +863,14 @@ __global__ __launch_bounds__(256) void k0_pack_admission(DeviceBatch d) {
     }
 }
 void launch_k0_pack_admission(const DeviceBatch& d, hipStream_t stream) {
-    if (!d.k2a_flat) return;
+    if (!d.n_adm) return;
     const uint64_t n = d.n_adm > d.n_exons_w ? d.n_adm : d.n_exons_w;
     hipLaunchKernelGGL(k0_pack_admission, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, stream, d);
     HIP_CHECK_LAUNCH();
 }
 #endif
 
-template <int W, int ITEMS>
+template <int W>
 __global__ __launch_bounds__(64) void k2a_admission_flat(DeviceBatch d) {
     struct In {
         bool on, rev, go;
@@ -1070,17 +1005,12 @@ __global__ __launch_bounds__(64) void k2a_admission_flat(DeviceBatch d) {
             }
         }
     };
-    In in0, in1;
-    load_entry(in0, blockIdx.x * ITEMS);
-    if constexpr (ITEMS == 2) load_entry(in1, blockIdx.x * ITEMS + 1);
+    In in0;
+    load_entry(in0, blockIdx.x);
     load_fields(in0);
-    if constexpr (ITEMS == 2) load_fields(in1);
     first_step(in0);
-    if constexpr (ITEMS == 2) first_step(in1);
     load_step(in0, in0.e.step_off + in0.t);   // (t = 0 where no step is tried: a valid address, the fields unused)
-    if constexpr (ITEMS == 2) load_step(in1, in1.e.step_off + in1.t);
     finish(in0);
-    if constexpr (ITEMS == 2) finish(in1);
 }
 
 // ====================================================================== K2l (lane-per-window replay)
@@ -1096,7 +1026,7 @@ __global__ __launch_bounds__(64) void k2a_admission_flat(DeviceBatch d) {
 // table in its LDS column instead (entry = haplotype word << 8 | count; linear probing; at most 63 distinct words, so a probe always ends
 // at a free slot): one dependent LDS round trip per row instead of the wave-per-window kernel's ballots and readlanes (470 wave
 // instructions per WINDOW there, ~40 here); the keys come out ascending by repeated minimum over the lane's occupied slots.
-template <int HB, int STAGE_, int GATHER_ = 8>   // STAGE_: RowRecs staged in LDS per pass (24 bytes each); 0 = straight from memory, GATHER_ rows at a time
+template <int HB, int STAGE_>   // STAGE_: RowRecs staged in LDS per pass (24 bytes each); 0 = straight from memory, GATHER_BLK rows at a time
 __global__ __launch_bounds__(64) void k2l_window_lanes(DeviceBatch d, uint32_t first, uint32_t count) {
     constexpr bool HASH = HB > 8;
     constexpr uint32_t NW = HASH ? 64u : (1u << HB) / 4;   // table words per lane (direct: four 8-bit counters each; hash: one entry each); NW <= 64
@@ -1186,7 +1116,7 @@ __global__ __launch_bounds__(64) void k2l_window_lanes(DeviceBatch d, uint32_t f
         if constexpr (STAGE_ == 0) {
             // (rows straight from memory: the loads of GATHER_BLK rows go out together, at clamped indices and unconditionally - a lane
             //  walks ~30 rows, and with one or two rows in flight every few rows cost a full memory round trip)
-            constexpr uint32_t GATHER_BLK = GATHER_;
+            constexpr uint32_t GATHER_BLK = 8;
             const uint32_t rn_max = wave_max(r_n);
             const uint32_t r_last = r_n ? r_n - 1 : 0u;
             const uint4* const ra = reinterpret_cast<const uint4*>(d.rr_a) + rr_lo;
@@ -1412,7 +1342,6 @@ __global__ __launch_bounds__(64) void k2w_window_rows(DeviceBatch d) {
     const ExonW e = d.exons_w[C.exon];
     const bool is_rev = e.strand != 0;
     const uint32_t rbase = e.rbase;
-    const uint32_t vbase = e.vbase;
     // the lanes hold a sliding block of 64 consecutive reads [L, L + 64) of the exon's candidate range; a window's rows are
     // the lanes inside its own range [r_lo, r_lo + r_n). The block moves only when a window's range leaves it.
     uint32_t L = 0;
@@ -1421,35 +1350,15 @@ __global__ __launch_bounds__(64) void k2w_window_rows(DeviceBatch d) {
     uint64_t q_sup = 0, q_dirty = 0;
     for (uint32_t s0 = 0; s0 < C.n_steps; s0 += 64) {
         const uint32_t nb = min(64u, C.n_steps - s0);
-        uint32_t w0 = 0, w2 = 0, w3 = 0, w4 = 0, w5 = 0, w6 = 0, w7 = 0, w8 = 0, w9 = 0;
-        if (lane < nb) {
-            const uint32_t si = C.step_first + s0 + lane;
-            const uint32_t* sp = reinterpret_cast<const uint32_t*>(d.steps + si);
-            w0 = sp[0]; w2 = sp[2]; w3 = sp[3]; w4 = sp[4]; w5 = sp[5];
-            w6 = d.step_rlo[si];
-            const uint32_t nc = d.step_ncols[si];
-            w7 = uint32_t(d.step_rn[si]) | (nc << 16);
-            if (((w5 >> 8) & SF_PRINT) && nc) {   // somatic columns of the step's window, already in haplotype bit order
-                uint32_t flo, fhi;
-                tr_to_f(e, is_rev, w2 - nc, w2, flo, fhi);
-                const uint64_t gv = uint64_t(vbase) + flo;
-                const uint64_t x0 = d.v_sombits[gv >> 6], x1 = d.v_sombits[(gv >> 6) + 1];
-                const uint32_t sh = uint32_t(gv & 63);
-                uint64_t bits = (sh ? ((x0 >> sh) | (x1 << (64 - sh))) : x0) & (~0ull >> (64 - nc));
-                if (!is_rev) bits = __brevll(bits) >> (64 - nc);
-                w8 = uint32_t(bits); w9 = uint32_t(bits >> 32);
-            }
-        }
-        // (the windows the lane-per-window kernel takes are not this kernel's: plan.cpp lane_window)
-        uint64_t printing = __ballot(lane < nb && ((w5 >> 8) & SF_PRINT) &&
-                                     !(d.lane_on && k2l_takes(w7 >> 16, w7 & 0xFFFF, d.lane_hash != 0)));
+        uint32_t w[10];
+        uint64_t printing = fetch_steps(d, e, is_rev, C.step_first + s0, nb, w);
         while (printing) {
             const uint32_t i = uint32_t(__builtin_ctzll(printing));
             printing &= printing - 1;
             const uint32_t si = C.step_first + s0 + i;
-            const uint32_t sso = rdlane(w0, i), col_hi = rdlane(w2, i), win = rdlane(w3, i);
-            const uint32_t p4 = rdlane(w4, i), p5 = rdlane(w5, i), r_lo = rdlane(w6, i), p7 = rdlane(w7, i);
-            const uint64_t som_mask = (uint64_t(rdlane(w9, i)) << 32) | rdlane(w8, i);
+            const uint32_t sso = rdlane(w[0], i), col_hi = rdlane(w[2], i), win = rdlane(w[3], i);
+            const uint32_t p4 = rdlane(w[4], i), p5 = rdlane(w[5], i), r_lo = rdlane(w[6], i), p7 = rdlane(w[7], i);
+            const uint64_t som_mask = (uint64_t(rdlane(w[9], i)) << 32) | rdlane(w[8], i);
             const uint32_t wlen = (p4 >> 16) & 0xFF, sflags = (p5 >> 8) & 0xFF;
             const uint32_t r_n = p7 & 0xFFFF, ncols = p7 >> 16;
             const uint32_t splice_end = sso + wlen;
@@ -1555,11 +1464,8 @@ __global__ __launch_bounds__(64) void k2w_window_rows(DeviceBatch d) {
             // group slots: exactly ng, from this wave's current chunk
             uint32_t werr = sticky_err;
             if (chunk_pos + ng > chunk_end) {
-                unsigned long long base = 0;
                 const uint32_t want = max(GROUP_CHUNK, ng);
-                if (lane == 0) base = atomicAdd(gcur, (unsigned long long)want);
-                const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                chunk_pos = gpart_lo + ((uint64_t(bhi) << 32) | blo);
+                chunk_pos = wave_claim(gcur, want, gpart_lo);
                 chunk_end = chunk_pos + want;
             }
             const bool can_write = chunk_end <= gpart_hi;
@@ -1571,11 +1477,8 @@ __global__ __launch_bounds__(64) void k2w_window_rows(DeviceBatch d) {
                 const uint64_t nm = __ballot(need);
                 const uint32_t nneed = __popcll(nm);
                 if (nneed && rec_pos + nneed > rec_end) {
-                    unsigned long long base = 0;
                     const uint32_t want = max(REC_CHUNK_W, nneed);
-                    if (lane == 0) base = atomicAdd(rcur, (unsigned long long)want);
-                    const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                    rec_pos = rpart_lo + ((uint64_t(bhi) << 32) | blo);
+                    rec_pos = wave_claim(rcur, want, rpart_lo);
                     rec_end = rec_pos + want;
                 }
                 uint32_t rec = 0xFFFFFFFFu;
@@ -1655,7 +1558,6 @@ __global__ __launch_bounds__(64) void k2w_window_rows_multi(DeviceBatch d) {
     const ExonW e = d.exons_w[C.exon];
     const bool is_rev = e.strand != 0;
     const uint32_t rbase = e.rbase;
-    const uint32_t vbase = e.vbase;
     uint32_t L = 0;
     bool have_block = false;
     uint32_t q_start[RPL], q_end[RPL], q_rvl[RPL], q_ord[RPL], q_seen[RPL];
@@ -1668,35 +1570,15 @@ __global__ __launch_bounds__(64) void k2w_window_rows_multi(DeviceBatch d) {
     }
     for (uint32_t s0 = 0; s0 < C.n_steps; s0 += 64) {
         const uint32_t nb = min(64u, C.n_steps - s0);
-        uint32_t w0 = 0, w2 = 0, w3 = 0, w4 = 0, w5 = 0, w6 = 0, w7 = 0, w8 = 0, w9 = 0;
-        if (lane < nb) {
-            const uint32_t si = C.step_first + s0 + lane;
-            const uint32_t* sp = reinterpret_cast<const uint32_t*>(d.steps + si);
-            w0 = sp[0]; w2 = sp[2]; w3 = sp[3]; w4 = sp[4]; w5 = sp[5];
-            w6 = d.step_rlo[si];
-            const uint32_t nc = d.step_ncols[si];
-            w7 = uint32_t(d.step_rn[si]) | (nc << 16);
-            if (((w5 >> 8) & SF_PRINT) && nc) {
-                uint32_t flo, fhi;
-                tr_to_f(e, is_rev, w2 - nc, w2, flo, fhi);
-                const uint64_t gv = uint64_t(vbase) + flo;
-                const uint64_t x0 = d.v_sombits[gv >> 6], x1 = d.v_sombits[(gv >> 6) + 1];
-                const uint32_t sh = uint32_t(gv & 63);
-                uint64_t bits = (sh ? ((x0 >> sh) | (x1 << (64 - sh))) : x0) & (~0ull >> (64 - nc));
-                if (!is_rev) bits = __brevll(bits) >> (64 - nc);
-                w8 = uint32_t(bits); w9 = uint32_t(bits >> 32);
-            }
-        }
-        // (the windows the lane-per-window kernel takes are not this kernel's: plan.cpp lane_window)
-        uint64_t printing = __ballot(lane < nb && ((w5 >> 8) & SF_PRINT) &&
-                                     !(d.lane_on && k2l_takes(w7 >> 16, w7 & 0xFFFF, d.lane_hash != 0)));
+        uint32_t w[10];
+        uint64_t printing = fetch_steps(d, e, is_rev, C.step_first + s0, nb, w);
         while (printing) {
             const uint32_t i = uint32_t(__builtin_ctzll(printing));
             printing &= printing - 1;
             const uint32_t si = C.step_first + s0 + i;
-            const uint32_t sso = rdlane(w0, i), col_hi = rdlane(w2, i), win = rdlane(w3, i);
-            const uint32_t p4 = rdlane(w4, i), p5 = rdlane(w5, i), r_lo = rdlane(w6, i), p7 = rdlane(w7, i);
-            const uint64_t som_mask = (uint64_t(rdlane(w9, i)) << 32) | rdlane(w8, i);
+            const uint32_t sso = rdlane(w[0], i), col_hi = rdlane(w[2], i), win = rdlane(w[3], i);
+            const uint32_t p4 = rdlane(w[4], i), p5 = rdlane(w[5], i), r_lo = rdlane(w[6], i), p7 = rdlane(w[7], i);
+            const uint64_t som_mask = (uint64_t(rdlane(w[9], i)) << 32) | rdlane(w[8], i);
             const uint32_t wlen = (p4 >> 16) & 0xFF, sflags = (p5 >> 8) & 0xFF;
             const uint32_t r_n = p7 & 0xFFFF, ncols = p7 >> 16;
             const uint32_t splice_end = sso + wlen;
@@ -1754,11 +1636,8 @@ __global__ __launch_bounds__(64) void k2w_window_rows_multi(DeviceBatch d) {
             nvalid += has_zero ? 0u : 1u;
             uint32_t werr = sticky_err;
             if (chunk_pos + nvalid > chunk_end) {
-                unsigned long long base = 0;
                 const uint32_t want = max(GROUP_CHUNK, nvalid);
-                if (lane == 0) base = atomicAdd(gcur, (unsigned long long)want);
-                const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                chunk_pos = gpart_lo + ((uint64_t(bhi) << 32) | blo);
+                chunk_pos = wave_claim(gcur, want, gpart_lo);
                 chunk_end = chunk_pos + want;
             }
             const bool can_write = chunk_end <= gpart_hi;
@@ -1771,11 +1650,8 @@ __global__ __launch_bounds__(64) void k2w_window_rows_multi(DeviceBatch d) {
                 const uint64_t nm = __ballot(need);
                 const uint32_t nneed = __popcll(nm);
                 if (nneed && rec_pos + nneed > rec_end) {
-                    unsigned long long base = 0;
                     const uint32_t want = max(REC_CHUNK_W, nneed);
-                    if (lane == 0) base = atomicAdd(rcur, (unsigned long long)want);
-                    const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                    rec_pos = rpart_lo + ((uint64_t(bhi) << 32) | blo);
+                    rec_pos = wave_claim(rcur, want, rpart_lo);
                     rec_end = rec_pos + want;
                 }
                 uint32_t rec = 0xFFFFFFFFu;
@@ -1927,18 +1803,12 @@ __global__ __launch_bounds__(64) void k2w_window_rows_deep(DeviceBatch d) {
         const uint32_t si = C.step_first + s;
         const Step st = d.steps[si];
         const uint32_t ncols = d.step_ncols[si], rn16 = d.step_rn[si];
-        if (!(st.flags & SF_PRINT) || (d.lane_on && ncols <= K2L_MAX_COLS && rn16 <= K2L_MAX_ROWS)) continue;   // (wave-uniform)
+        if (!(st.flags & SF_PRINT) || k2l_takes(d.lane_on != 0, ncols, rn16)) continue;   // (wave-uniform; the lane kernel's windows: plan.cpp lane_window)
         const uint32_t sso = st.sso, col_hi = st.col_hi, win = st.win, splice_end = st.sso + st.wlen, r_lo = d.step_rlo[si];
         uint64_t som_mask = 0;
         uint32_t flo = 0, fhi = 0;
         tr_to_f(e, is_rev, col_hi - ncols, col_hi, flo, fhi);
-        if (ncols) {
-            const uint64_t gv = uint64_t(vbase) + flo;
-            const uint64_t x0 = d.v_sombits[gv >> 6], x1 = d.v_sombits[(gv >> 6) + 1];
-            const uint32_t sh = uint32_t(gv & 63);
-            som_mask = (sh ? ((x0 >> sh) | (x1 << (64 - sh))) : x0) & (~0ull >> (64 - ncols));
-            if (!is_rev) som_mask = __brevll(som_mask) >> (64 - ncols);
-        }
+        if (ncols) som_mask = somatic_mask(d.v_sombits, uint64_t(vbase) + flo, ncols, is_rev);
         const uint64_t cmask = ncols ? (~0ull >> (64 - ncols)) : 0ull;
         uint32_t nrows = 0;
         bool zero_here = false;
@@ -2004,9 +1874,7 @@ __global__ __launch_bounds__(64) void k2w_window_rows_deep(DeviceBatch d) {
         bitonic_sort_wave<uint64_t>(skey, N, lane);
         const uint32_t lead = has_zero ? 0u : 1u;   // the zero-count reference group goes first (:429-431)
         const uint32_t ng = n_distinct + lead;
-        unsigned long long gb = 0;
-        if (lane == 0) gb = atomicAdd(gcur, (unsigned long long)ng);
-        const uint64_t gbase_rel = (uint64_t(rdlane(uint32_t(gb >> 32), 0)) << 32) | rdlane(uint32_t(gb), 0);
+        const uint64_t gbase_rel = wave_claim(gcur, ng, 0);
         const bool can_write = gbase_rel + ng <= gpart_size;
         uint32_t werr = sticky_err;
         if (!can_write) werr |= WD_GROUP_OVERFLOW;
@@ -2027,11 +1895,8 @@ __global__ __launch_bounds__(64) void k2w_window_rows_deep(DeviceBatch d) {
             const uint64_t nm = __ballot(need);
             const uint32_t nneed = __popcll(nm);
             if (nneed && rec_pos + nneed > rec_end) {
-                unsigned long long base = 0;
                 const uint32_t want = max(64u, nneed);
-                if (lane == 0) base = atomicAdd(rcur, (unsigned long long)want);
-                const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                rec_pos = rpart_lo + ((uint64_t(bhi) << 32) | blo);
+                rec_pos = wave_claim(rcur, want, rpart_lo);
                 rec_end = rec_pos + want;
             }
             uint32_t rec = 0xFFFFFFFFu;
@@ -2314,20 +2179,14 @@ __global__ __launch_bounds__(64) void k2n_window_replay(DeviceBatch d) {
             uint32_t werr = sticky_err;
             // group slots + one HapRec slot per haplotype (every haplotype of every window can be emitted in this mode)
             if (chunk_pos + ng > chunk_end) {
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(gcur, (unsigned long long)K2N_GROUP_CHUNK);
-                const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                chunk_pos = gpart_lo + ((uint64_t(bhi) << 32) | blo);
+                chunk_pos = wave_claim(gcur, K2N_GROUP_CHUNK, gpart_lo);
                 chunk_end = chunk_pos + K2N_GROUP_CHUNK;
             }
             const bool can_write = chunk_end <= gpart_hi;
             if (!can_write) werr |= WD_GROUP_OVERFLOW;
             if (can_write && rec_pos + ng > rec_end) {
                 const uint32_t want = max(uint32_t(REC_CHUNK), ng);
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(rcur, (unsigned long long)want);
-                const uint32_t blo = rdlane(uint32_t(base), 0), bhi = rdlane(uint32_t(base >> 32), 0);
-                rec_pos = rpart_lo + ((uint64_t(bhi) << 32) | blo);
+                rec_pos = wave_claim(rcur, want, rpart_lo);
                 rec_end = rec_pos + want;
             }
             if (can_write && rec_pos + ng > rpart_hi) sticky_err |= WD_REC_OVERFLOW;
@@ -3187,20 +3046,12 @@ void launch_k2_window_replay(const DeviceBatch& d, int rows_per_lane, hipStream_
 #endif
 #if MP_IN_PART(0)
 void launch_k2_admission(const DeviceBatch& d, hipStream_t stream) {
-    if (!d.n_exons_w) return;
-    if (!d.n_achunks) return;
-    if (d.k2a_flat && d.mask_words <= 2) {
-        // (entries per lane: 1 measured 0.389 ms, 2 0.405 ms, the chunk form 0.418 ms on one box - the kernel is not short of loads in flight)
-        const char* env_items = std::getenv("MP_K2A_ITEMS");
-        const int items = env_items && std::atoi(env_items) == 2 ? 2 : 1;
-        const uint32_t waves = uint32_t((d.n_adm + 63) / 64), grid = (waves + items - 1) / items;
-        if (d.mask_words == 1) { if (items == 2) hipLaunchKernelGGL((k2a_admission_flat<1, 2>), dim3(grid), dim3(64), 0, stream, d); else hipLaunchKernelGGL((k2a_admission_flat<1, 1>), dim3(grid), dim3(64), 0, stream, d); }
-        else { if (items == 2) hipLaunchKernelGGL((k2a_admission_flat<2, 2>), dim3(grid), dim3(64), 0, stream, d); else hipLaunchKernelGGL((k2a_admission_flat<2, 1>), dim3(grid), dim3(64), 0, stream, d); }
-        HIP_CHECK_LAUNCH();
-        return;
-    }
-    if (d.mask_words == 1) hipLaunchKernelGGL(k2a_admission<1>, dim3(d.n_achunks), dim3(64), 0, stream, d);
-    else if (d.mask_words == 2) hipLaunchKernelGGL(k2a_admission<2>, dim3(d.n_achunks), dim3(64), 0, stream, d);
+    if (!d.n_adm) return;
+    // (one entry per lane measured 0.389 ms, two 0.405 ms, a wave per <= 64 reads of one exon 0.418 ms on one box - the kernel is not
+    //  short of loads in flight). n_adm <= ADM_MAX (plan.hpp): the grid's lanes and the kernel's 32-bit entry indices stay below 2^32.
+    const dim3 grid(uint32_t((d.n_adm + 63) / 64)), block(64);
+    if (d.mask_words == 1) hipLaunchKernelGGL(k2a_admission_flat<1>, grid, block, 0, stream, d);
+    else if (d.mask_words == 2) hipLaunchKernelGGL(k2a_admission_flat<2>, grid, block, 0, stream, d);
     else throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
     HIP_CHECK_LAUNCH();
 }
@@ -3238,47 +3089,28 @@ void launch_k2_window_rows(const DeviceBatch& d, hipStream_t stream) {
 
 #endif
 #if MP_IN_PART(0)
-template <int STAGE>
-static void launch_k2l(const DeviceBatch& d, hipStream_t stream_small, hipStream_t stream_wide, hipStream_t stream_hash) {
+void launch_k2_window_lanes(const DeviceBatch& d, hipStream_t stream_small, hipStream_t stream_wide, hipStream_t stream_hash) {
+    if (!d.lane_on) return;
     // one wave per tile of 64 windows: a wave that walked several tiles would wait for its own result stores to drain before the
     // next tile's loads return (loads and stores share the in-order vmcnt counter)
     const uint32_t n_small = d.n_lane_small, n_wide = d.n_lane_mid - d.n_lane_small, n_hash = d.n_lane_all - d.n_lane_mid;
-    const uint32_t lds_small = 4096 + 24 * STAGE, lds_wide = 16384 + 24 * STAGE;
-    static const bool persistent = std::getenv("MP_K2L_PERSISTENT") != nullptr;   // experiments: a fixed grid that walks the tiles
-    static const bool gather16 = [] { const char* e = std::getenv("MP_K2L_GATHER"); return e && std::atoi(e) == 16; }();   // rows fetched together by the gather forms (default 8)
     if (n_small) {
-        const uint32_t tiles = (n_small + 63) / 64, waves = min(32u, 163840u / lds_small);
-        hipLaunchKernelGGL((k2l_window_lanes<K2L_SMALL_COLS, STAGE>), dim3(persistent ? min(tiles, 256u * waves) : tiles), dim3(64), 0, stream_small, d, 0u, n_small);
+        hipLaunchKernelGGL((k2l_window_lanes<K2L_SMALL_COLS, 256>), dim3((n_small + 63) / 64), dim3(64), 0, stream_small, d, 0u, n_small);
         HIP_CHECK_LAUNCH();
     }
     if (n_wide) {
         // The windows of 7-8 columns are a sparse subset too (a fifth of the lane kernel's windows): their tiles span several exons and
         // need several staging passes; reading the records straight from memory is faster for them (window phase 1.15 -> 1.05 ms at
-        // config C, same box); MP_K2L_WIDE_STAGED=1 brings the staged form back for comparisons.
-        static const bool wide_gather = std::getenv("MP_K2L_WIDE_STAGED") == nullptr;
-        const uint32_t tiles = (n_wide + 63) / 64, waves = min(32u, 163840u / lds_wide);
-        if (wide_gather && gather16) hipLaunchKernelGGL((k2l_window_lanes<K2L_MAX_COLS, 0, 16>), dim3(tiles), dim3(64), 0, stream_wide, d, n_small, n_wide);
-        else if (wide_gather) hipLaunchKernelGGL((k2l_window_lanes<K2L_MAX_COLS, 0>), dim3(tiles), dim3(64), 0, stream_wide, d, n_small, n_wide);
-        else hipLaunchKernelGGL((k2l_window_lanes<K2L_MAX_COLS, STAGE>), dim3(persistent ? min(tiles, 256u * waves) : tiles), dim3(64), 0, stream_wide, d, n_small, n_wide);
+        // config C, same box).
+        hipLaunchKernelGGL((k2l_window_lanes<K2L_MAX_COLS, 0>), dim3((n_wide + 63) / 64), dim3(64), 0, stream_wide, d, n_small, n_wide);
         HIP_CHECK_LAUNCH();
     }
     if (n_hash) {   // 9..16 columns: the per-lane hash table (16 KB of LDS per wave, as the 7-8 column form)
         // These windows are a sparse subset (7.5 % at config C): the 64 windows of a tile come from many exons, their candidate ranges do
         // not overlap, and staging them through LDS took one pass - barrier, reductions, a round of loads - per WINDOW (1.36 ms for
         // 0.66 M windows). Every lane reads its own window's records straight from memory instead (two loads in flight ahead).
-        const uint32_t tiles = (n_hash + 63) / 64, waves = min(32u, 163840u / 16384u);
-        if (gather16) hipLaunchKernelGGL((k2l_window_lanes<K2L_HASH_COLS, 0, 16>), dim3(tiles), dim3(64), 0, stream_hash, d, d.n_lane_mid, n_hash);
-        else hipLaunchKernelGGL((k2l_window_lanes<K2L_HASH_COLS, 0>), dim3(persistent ? min(tiles, 256u * waves) : tiles), dim3(64), 0, stream_hash, d, d.n_lane_mid, n_hash);
+        hipLaunchKernelGGL((k2l_window_lanes<K2L_HASH_COLS, 0>), dim3((n_hash + 63) / 64), dim3(64), 0, stream_hash, d, d.n_lane_mid, n_hash);
         HIP_CHECK_LAUNCH();
-    }
-}
-void launch_k2_window_lanes(const DeviceBatch& d, hipStream_t stream_small, hipStream_t stream_wide, hipStream_t stream_hash) {
-    if (!d.lane_on) return;
-    static const int stage = [] { const char* e = std::getenv("MP_K2L_STAGE"); return e ? std::atoi(e) : 256; }();   // experiments
-    switch (stage) {
-        case 0: launch_k2l<0>(d, stream_small, stream_wide, stream_hash); break;
-        case 384: launch_k2l<384>(d, stream_small, stream_wide, stream_hash); break;
-        default: launch_k2l<256>(d, stream_small, stream_wide, stream_hash); break;
     }
 }
 
@@ -3292,12 +3124,11 @@ void launch_k3_list(const DeviceBatch& d, uint64_t max_items, hipStream_t stream
     // one wave per workgroup for all lists. (List A in 256-thread workgroups - four waves sharing one 2 KB decimal-text table, 12
     // instead of 11 waves per CU - measured 1.55 against 1.46 ms: the four waves of a workgroup start together and stay in step, gather
     // phase on gather phase; the instantiations were dropped again.)
-    static const int items = [] { const char* e = std::getenv("MP_K3_ITEMS"); return e && std::atoi(e) == 1 ? 1 : 2; }();   // list entries per lane (1: the round-2 form)
     const int T = K3_THREADS;
     // (two entries per lane pay where the list fills the chip several times over - 7 M entries of list A at config C: 1.45 -> 1.37 ms; a
     //  short list - list D, every list of a small batch - is a single round of waves, whose length two entries per lane would double:
     //  config B 0.41 -> 0.46 ms when lists C and D arrived with two)
-    const int U = d.seq_cap <= 48 && max_items >= 640 * 1024 ? items : 1;
+    const int U = d.seq_cap <= 48 && max_items >= 640 * 1024 ? 2 : 1;   // list entries per lane
     const uint64_t per_wave = uint64_t(T) * uint64_t(U);
     const uint64_t per_list = max_items / NPART + max_items / (4 * NPART) + per_wave;
     dim3 grid(uint32_t(std::min<uint64_t>((per_list + per_wave - 1) / per_wave, 0x7FFFFFFFull)), NPART), block(T);

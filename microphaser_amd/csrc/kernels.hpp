@@ -31,7 +31,6 @@ struct DeviceBatch {  // device pointers (all hipMalloc'ed by DeviceContext)
     const WinCol* win_cols;
     ExonA* exons_a;               // per window-parallel exon / per admission-table entry, packed on the device at upload (launch_k0_pack_admission)
     AdmMap* adm_map;
-    uint32_t k2a_flat, k2a_pad_;  // the flat form of K2a (a lane per table entry across exon boundaries); MP_K2A_CHUNKS=1: a wave per <= 64 reads of ONE exon
     WinBlob* win_blobs;           // one per window, packed on the device at upload (launch_k0_pack_windows); somatic mode only
     const uint8_t* str_pool;
     const SegDev* segs;           // replay units (K2 / K2n launch one wave per segment)
@@ -42,7 +41,6 @@ struct DeviceBatch {  // device pointers (all hipMalloc'ed by DeviceContext)
     const WChunk* wchunks;          // work items of k2w_window_rows (<= 64 candidate reads per window, one mask word)
     const WChunk* wchunks_m;        // work items of k2w_window_rows_multi (deeper exons, or two mask words)
     const WChunk* wchunks_d;        // work items of k2w_window_rows_deep (more than 512 candidate reads per window)
-    uint32_t n_wchunks_d, lane_hash;   // lane_hash: the lane kernel also takes the windows of 9..16 columns (plan.hpp k2l_takes)
     const uint8_t* step_ncols;
     const uint32_t* step_rlo;
     const uint16_t* step_rn;
@@ -57,9 +55,7 @@ struct DeviceBatch {  // device pointers (all hipMalloc'ed by DeviceContext)
     const uint32_t* win_walk;       // bit per window: !WSF_SIMPLE (needs the general sequence walk: list D)
     const uint32_t* win_simple;     // bit per window: WSF_SIMPLE && WSF_NOSTOP
     uint32_t n_lane_small, n_lane_all, lane_on, n_lane_mid;   // winw[0, small): <= 6 columns, [small, mid): 7-8, [mid, all): 9-16 (hash form)
-    const WChunk* achunks;          // work items of k2a_admission: (exon, first read of the exon's range, count <= 64)
-    const ExonW* achunk_exons;      // the exon record of every admission work item, beside it (one load level less in a latency-bound kernel)
-    uint32_t n_exons_w, n_wchunks, n_wchunks_m, n_achunks;
+    uint32_t n_exons_w, n_wchunks, n_wchunks_m, n_wchunks_d;
     uint32_t rows_per_lane_w;       // RPL of k2w_window_rows_multi: 64 * RPL >= candidate reads of any of its windows
     uint64_t n_adm;
     uint32_t n_reads, n_tx, n_wins, mask_words;

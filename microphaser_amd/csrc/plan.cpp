@@ -478,7 +478,7 @@ static void validate_segments(const Batch& b) {
 // Lane-per-window replay (plan.hpp WinW): flatten every eligible printing window of the window-parallel exons, small windows
 // (<= K2L_SMALL_COLS columns) first; the wave-per-window kernels keep only the work items that still hold one of their windows.
 static bool lane_window(const Batch& b, uint32_t si) {
-    return b.lane_on && (b.steps[si].flags & SF_PRINT) && k2l_takes(b.step_ncols[si], b.step_rn[si], b.lane_hash);
+    return (b.steps[si].flags & SF_PRINT) && k2l_takes(b.lane_on, b.step_ncols[si], b.step_rn[si]);
 }
 static void route_lane_windows(Batch& b) {
     b.winw.clear();
@@ -586,10 +586,8 @@ static void route_window_parallel(Batch& b) {
     if (b.seg_info.size() != b.segs.size()) throw Error("internal error: segment info out of step");
     const bool enabled = !b.normal && b.mask_words <= 2 && !std::getenv("MP_SEQUENTIAL_REPLAY");
     b.lane_on = enabled && b.mask_words == 1 && !std::getenv("MP_NO_LANE_KERNEL");
-    b.lane_hash = b.lane_on && !std::getenv("MP_NO_LANE_HASH");   // (measurements: the 9..16-column windows back to the wave kernels)
     b.wchunks_m.clear();
     b.wchunks_d.clear();
-    b.achunks.clear();
     uint32_t max_rn_multi = 0;
     PodVec<SegDev> keep;
     constexpr uint32_t CHUNK_STEPS = 96;
@@ -599,7 +597,7 @@ static void route_window_parallel(Batch& b) {
     struct Part {
         PodVec<SegDev> keep;
         PodVec<ExonW> exons;
-        PodVec<WChunk> achunks, wchunks, wchunks_m, wchunks_d;
+        PodVec<WChunk> wchunks, wchunks_m, wchunks_d;
         uint64_t n_adm = 0;
         uint32_t max_rn_multi = 0;
         std::string error;
@@ -624,7 +622,7 @@ static void route_window_parallel(Batch& b) {
         ExonW e{};
         e.tx = g.tx; e.step_off = g.step_off; e.n_steps = g.n_steps;
         e.read_lo = read_lo; e.n_reads = read_hi - read_lo;
-        if (P.n_adm + e.n_reads > 0xFFFFFFF0ull) throw Error("batch too large for 32-bit admission-table offsets: split the batch by genes");
+        if (P.n_adm + e.n_reads > ADM_MAX) throw Error("batch too large for 32-bit admission-table offsets: split the batch by genes");
         e.adm_off = uint32_t(P.n_adm);   // (range-local: rebased when the ranges are joined)
         P.n_adm += e.n_reads;
         e.first_key_lo = si.first_key_lo; e.range = si.range; e.tr0 = si.tr0; e.f0 = si.f0;
@@ -648,7 +646,6 @@ static void route_window_parallel(Batch& b) {
         }
         const uint32_t ei = uint32_t(P.exons.size());   // (range-local)
         P.exons.push_back(e);
-        for (uint32_t k0 = 0; k0 < e.n_reads; k0 += 64) P.achunks.push_back(WChunk{ei, k0, std::min(64u, e.n_reads - k0), 0});
         const bool multi = si.max_rn > 63 || b.mask_words > 1;   // needs several reads per lane / two mask words (63: rows + the reference haplotype fit 64 lanes)
         const bool deep = si.max_rn > 512;                        // beyond the resident block of the multi kernel: rows are streamed
         if (multi && !deep) P.max_rn_multi = std::max(P.max_rn_multi, si.max_rn);
@@ -677,7 +674,7 @@ static void route_window_parallel(Batch& b) {
     for (const Part& P : parts) if (!P.error.empty()) throw Error(P.error);
     for (Part& P : parts) {   // join in segment order: exon indices and admission offsets move by what came before
         const uint32_t e0 = uint32_t(b.exons_w.size());
-        if (b.n_adm + P.n_adm > 0xFFFFFFF0ull) throw Error("batch too large for 32-bit admission-table offsets: split the batch by genes");
+        if (b.n_adm + P.n_adm > ADM_MAX) throw Error("batch too large for 32-bit admission-table offsets: split the batch by genes");
         const uint32_t a0 = uint32_t(b.n_adm);
         for (ExonW& e : P.exons) e.adm_off += a0;
         b.exons_w.insert(b.exons_w.end(), P.exons.begin(), P.exons.end());
@@ -685,7 +682,7 @@ static void route_window_parallel(Batch& b) {
             for (WChunk& c : src) c.exon += e0;
             dst.insert(dst.end(), src.begin(), src.end());
         };
-        take(b.achunks, P.achunks); take(b.wchunks, P.wchunks); take(b.wchunks_m, P.wchunks_m); take(b.wchunks_d, P.wchunks_d);
+        take(b.wchunks, P.wchunks); take(b.wchunks_m, P.wchunks_m); take(b.wchunks_d, P.wchunks_d);
         keep.insert(keep.end(), P.keep.begin(), P.keep.end());
         b.n_adm += P.n_adm;
         max_rn_multi = std::max(max_rn_multi, P.max_rn_multi);

@@ -51,11 +51,14 @@ struct SegDev {
 // consecutive variant indices, with at most 64 candidate reads per window and W = 1, needs no sequential state machine:
 // a read's admission step follows from its K1 masks and the plan (K2a), and the rows of a window are then a closed form
 // of (admission step, read span, masks, live column range) - one wave per run of windows (K2w).
+// Admission-table entries per batch (the planner refuses more): K2a's grid of 64-lane waves must stay below 2^32 lanes, and its 32-bit
+// entry indices, adm_off and the RowRec index WinW::rr_lo then never wrap.
+constexpr uint64_t ADM_MAX = 0xFFFFFF00ull;
 struct ExonW {
     uint32_t tx;
     uint32_t step_off, n_steps;
     uint32_t read_lo, n_reads;      // gene-relative range of the reads that can be candidates in this exon
-    uint32_t adm_off;               // first AdmEntry of the exon (one per read of the range)
+    uint32_t adm_off;               // first AdmEntry of the exon (one per read of the range); the table holds at most ADM_MAX entries
     uint32_t first_key_lo;          // '+': lowest start key of the first window's candidate range (:1229-1248)
     uint32_t range;                 // '-': candidate key range extent R - candidates have start in [sso - R, sso] (:1198-1226)
     uint32_t tr0, f0;               // transcription-order index -> forward index: f = strand ? f0 - (tr - tr0) : tr
@@ -72,8 +75,8 @@ struct ExonW {
 };
 enum : uint32_t { EW_WAVE = 1,      // a wave-per-window kernel has a window here: AdmEntry
                   EW_LANE = 2 };    // the lane-per-window kernel has one: RowRec
-// What K2a needs of an ExonW, in four 16-byte loads (packed on the device at upload, k0_pack_admission); the flat form of K2a gives every
-// lane one (exon, read) entry of the admission table, whatever exon it belongs to, so the exon's fields are per-lane values there.
+// What K2a needs of an ExonW, in four 16-byte loads (packed on the device at upload, k0_pack_admission); K2a gives every lane one
+// (exon, read) entry of the admission table, whatever exon it belongs to, so the exon's fields are per-lane values there.
 struct ExonA {
     uint32_t step_off, n_steps, unit_steps, sso0;
     uint32_t sso1, first_key_lo, range, tr0;
@@ -101,12 +104,13 @@ constexpr uint32_t K2L_SMALL_COLS = 6;    // windows with <= 6 columns: 64 count
 constexpr uint32_t K2L_MAX_ROWS = 255;    // 8-bit counters
 constexpr uint32_t K2L_HASH_COLS = 16;    // windows with 9..16 columns: a 64-slot hash table per lane (entry = 16-bit haplotype word << 8 | count) ...
 constexpr uint32_t K2L_HASH_ROWS = 63;    // ... which must keep a free slot: at most 63 candidate reads (so at most 63 distinct words)
-// does the lane-per-window kernel take a printing window with this many columns / candidate reads? (planner and wave kernels agree on it)
+// does the lane-per-window kernel (lane_on: it runs in this batch) take a printing window with this many columns / candidate reads? The
+// planner (plan.cpp lane_window) and the three wave-per-window kernels decide by this alone: they skip exactly the windows it takes.
 #if defined(__HIPCC__) || defined(__CUDACC__)
 __host__ __device__
 #endif
-inline bool k2l_takes(uint32_t ncols, uint32_t rn, bool hash_form) {
-    return (ncols <= K2L_MAX_COLS && rn <= K2L_MAX_ROWS) || (hash_form && ncols <= K2L_HASH_COLS && rn <= K2L_HASH_ROWS);
+inline bool k2l_takes(bool lane_on, uint32_t ncols, uint32_t rn) {
+    return lane_on && ((ncols <= K2L_MAX_COLS && rn <= K2L_MAX_ROWS) || (ncols <= K2L_HASH_COLS && rn <= K2L_HASH_ROWS));
 }
 struct WinW {
     uint32_t rr_lo;      // RowRec index of the window's first candidate read

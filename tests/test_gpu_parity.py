@@ -694,38 +694,63 @@ def test_gpu_three_way_splice_equals_the_oracle_and_reports(ctx, tmp_path, capsy
 def test_gpu_lane_per_window_and_wave_per_window_replay_agree(ctx, monkeypatch):
     """K2l (lane per window: RowRecs + per-lane LDS counters) against K2w (wave per window) on the same exome: the default plan
     sends the windows with <= 8 columns to K2l, MP_NO_LANE_KERNEL=1 sends everything to K2w. Shallow and deep (rows spread over
-    more than 64 reads: the multi-block wave kernel keeps the wide windows, the lane kernel takes the narrow ones)."""
+    more than 64 reads: the multi-block wave kernel keeps the wide windows, the lane kernel takes the narrow ones). The number of
+    hashed haplotype ids does not depend on which kernel took a window."""
     for seed, n, depth, spacing in ((4243, 50, 30.0, 5.4), (4244, 30, 45.0, 2.5), (4245, 8, 150.0, 9.0)):
         ds = ctx.synth(seed, n, depth, spacing)
         monkeypatch.delenv("MP_NO_LANE_KERNEL", raising=False)
         b = ds.batch()
-        b.run()
+        st = b.run()
         lanes = b.results()
         monkeypatch.setenv("MP_NO_LANE_KERNEL", "1")
         b2 = ds.batch()
-        b2.run()
+        st2 = b2.run()
         waves = b2.results()
         assert (lanes.fasta, lanes.normal_fasta, lanes.tsv, lanes.windows) == (waves.fasta, waves.normal_fasta, waves.tsv, waves.windows)
+        assert st.n_windows_lane > 0 and st2.n_windows_lane == 0
+        assert st.n_ids == st2.n_ids
         assert lanes.tsv.count(b"\n") > 200
     monkeypatch.delenv("MP_NO_LANE_KERNEL", raising=False)
 
 
-def test_gpu_flat_and_per_exon_admission_agree(ctx, monkeypatch):
-    """K2a in its flat form (a lane per (exon, read) entry across exon boundaries, the exon's fields packed on the device at upload)
-    against the form with a wave per <= 64 reads of ONE exon (MP_K2A_CHUNKS=1), one and two entries per lane: same bytes - on an exome
-    with both strands, indels, multi-allelic sites and soft-masked reference (exons of both kinds: window-parallel and sequential)
-    and on a deep one (two mask words per read)."""
+def test_gpu_deep_exons_leave_the_lane_kernels_windows_to_it(ctx, monkeypatch):
+    """Exons with more than 512 candidate reads per window go to k2w_window_rows_deep, but their edge windows can have few reads: a
+    window of 9..16 columns and <= 63 reads is the lane kernel's (plan.hpp k2l_takes). The deep kernel used to compute such a window a
+    second time, with groups of its own that the output never showed. Against MP_NO_LANE_KERNEL=1 (every window through the wave
+    kernels): the same bytes, the same hashed ids and - both kernels at work here take exactly the group slots a window needs - the same
+    number of group slots."""
+    ds = ctx.synth(22, 20, 1000.0, 2.5)   # one mask word per read; 20 windows of 9..16 columns for the lane kernel, one in a deep work item
+    monkeypatch.delenv("MP_NO_LANE_KERNEL", raising=False)
+    b = ds.batch()
+    st = b.run()
+    lanes = b.results()
+    monkeypatch.setenv("MP_NO_LANE_KERNEL", "1")
+    b2 = ds.batch()
+    st2 = b2.run()
+    waves = b2.results()
+    monkeypatch.delenv("MP_NO_LANE_KERNEL", raising=False)
+    assert st.n_steps_seq == 0 and st.n_windows_lane > 0 and st2.n_windows_lane == 0
+    assert (lanes.fasta, lanes.normal_fasta, lanes.tsv, lanes.windows) == (waves.fasta, waves.normal_fasta, waves.tsv, waves.windows)
+    assert st.n_ids == st2.n_ids
+    assert st.n_groups == st2.n_groups, (st.n_groups, st2.n_groups)
+    assert lanes.tsv.count(b"\n") > 1000
+
+
+def test_gpu_window_parallel_and_sequential_replay_agree_gene_by_gene(ctx, monkeypatch):
+    """K2a (a lane per (exon, read) entry across exon boundaries, the exon's fields packed on the device at upload) + the window kernels
+    against the sequential replay (MP_SEQUENTIAL_REPLAY=1: no K2a at all): same bytes - on an exome with both strands, indels,
+    multi-allelic sites and soft-masked reference (exons of both kinds: window-parallel and sequential) and on a deep one (two mask
+    words per read). A gene on which the reference itself would panic fails the same way under both."""
+    import microphaser_amd as m
     for seed, n, depth, spacing, kw in ((5151, 60, 30.0, 5.4, {}), (5152, 40, 35.0, 6.0, dict(indel_rate=0.05, multiallelic_rate=0.05, softmask_rate=0.1)),
                                         (5153, 6, 400.0, 1.6, {})):
-        import microphaser_amd as m
         ds = ctx.synth(seed, n, depth, spacing, **kw)
         got = []
-        for env in ({}, {"MP_K2A_ITEMS": "2"}, {"MP_K2A_CHUNKS": "1"}):
-            for k in ("MP_K2A_ITEMS", "MP_K2A_CHUNKS"):
-                monkeypatch.delenv(k, raising=False)
+        for env in ({}, {"MP_SEQUENTIAL_REPLAY": "1"}):
+            monkeypatch.delenv("MP_SEQUENTIAL_REPLAY", raising=False)
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
-            per_gene = []   # the whole exome in one batch, then gene by gene: a gene on which the reference itself would panic must fail the same way in every form
+            per_gene = []   # the whole exome in one batch, then gene by gene
             for g in [None] + list(range(ds.num_genes)):
                 b = ds.batch() if g is None else ds.batch(gene_lo=g, gene_hi=g + 1)
                 try:
@@ -737,10 +762,9 @@ def test_gpu_flat_and_per_exon_admission_agree(ctx, monkeypatch):
                     per_gene.append(str(e))
                 b.close()
             got.append(per_gene)
-        assert got[0] == got[1] == got[2]
+        assert got[0] == got[1]
         assert sum(x[2].count(b"\n") for x in got[0] if not isinstance(x, str)) > 100
-    for k in ("MP_K2A_ITEMS", "MP_K2A_CHUNKS"):
-        monkeypatch.delenv(k, raising=False)
+    monkeypatch.delenv("MP_SEQUENTIAL_REPLAY", raising=False)
 
 
 def test_gpu_chunked_overlapped_phasing_equals_the_single_batch(ctx):
