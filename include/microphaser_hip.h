@@ -234,6 +234,14 @@ int mp_translate(mp_ctx* ctx, const uint8_t* nt, const uint8_t* reverse, uint64_
  * holds counts[a] * mp_key_words(peptide_len) words (need not be 16-byte aligned); sorted and distinct in key order (for two-word keys:
  * the high word first). Host-side merge of sorted runs; no GPU needed. */
 int mp_peptides_union(mp_ctx* ctx, const uint64_t* const* keys, const uint64_t* counts, uint32_t n_arrays, uint32_t peptide_len, mp_peptides** out);
+/* `normal` -> `build_reference` without the nucleotide FASTA: the peptidome of exactly the records mp_batch_results would
+ * write to the `normal` FASTA stream, translated on the GPU from the device-resident haplotype sequences (reference:
+ * src/normal_microphasing.rs print + merge, src/peptides.rs:148-186). streams: text streams wanted from the same consumer pass
+ * (0 = none; results may then be NULL). Same keys, count and bincode image as mp_peptidome_from_buffer on that FASTA.
+ * Call after mp_batch_run of a MP_MODE_NORMAL batch; fails like mp_batch_results if another batch ran on the context since,
+ * and on a host-only context (no CPU fallback). 1 <= peptide_len <= 25. The returned peptidome's FASTA is empty. */
+int mp_batch_peptidome(mp_ctx* ctx, mp_batch* batch, uint32_t peptide_len, uint32_t streams, mp_results** results,
+                       mp_peptides** out);
 
 /* `microphaser filter` (reference: peptides::filter, src/peptides.rs:221-709 <- run_filtering, src/main.rs:170-214,
  * src/filter_cli.yaml): translate the mutant / normal windows of a `somatic` info.tsv, drop self-similar, repeated and

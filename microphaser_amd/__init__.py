@@ -185,6 +185,7 @@ def lib():
         "mp_batch_run": (i32, [vp, vp, ctypes.POINTER(RunStats)]),
         "mp_batch_results": (i32, [vp, vp, pp]),
         "mp_batch_results_select": (i32, [vp, vp, u32, pp]),
+        "mp_batch_peptidome": (i32, [vp, vp, u32, u32, pp, pp]),
         "mp_batch_free": (None, [vp]),
         "mp_phase_dataset": (i32, [vp, vp, i32, u64, pp]),
         "mp_results_fasta": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
@@ -231,7 +232,7 @@ C_ABI_SYMBOLS = [
     "mp_filtered_removed_fasta", "mp_filtered_count", "mp_filtered_free",
     "mp_synth_gene_costs", "mp_dataset_from_arrays", "mp_dataset_to_arrays", "mp_gene_batch_free", "mp_dataset_gene_costs",
     "mp_batch_create_genes", "mp_results_gene_offsets", "mp_translate", "mp_peptides_union", "mp_build_reference_buffer", "mp_peptidome_from_buffer",
-    "mp_batch_results_dump", "mp_batch_results_from_dump", "mp_peptides_key_words", "mp_key_words",
+    "mp_batch_results_dump", "mp_batch_results_from_dump", "mp_peptides_key_words", "mp_key_words", "mp_batch_peptidome",
 ]
 
 
@@ -537,6 +538,15 @@ class Batch:
         h = ctypes.c_void_p()
         self.ctx._check(lib().mp_batch_results_select(self.ctx._h, self._h, streams, ctypes.byref(h)))
         return Results(h)
+
+    def peptidome(self, peptide_len=9, streams=0):
+        """`normal` -> `build_reference` in one step (mp_batch_peptidome): the peptidome of the records results() would write to the
+        FASTA stream, translated on the GPU from the device-resident haplotype sequences - no nucleotide FASTA in between. Returns
+        (Peptides, Results of the streams asked for in the same consumer pass, or None when streams == 0)."""
+        hp, hr = ctypes.c_void_p(), ctypes.c_void_p()
+        self.ctx._check(lib().mp_batch_peptidome(self.ctx._h, self._h, peptide_len, streams, ctypes.byref(hr) if streams else None,
+                                                 ctypes.byref(hp)))
+        return Peptides(hp, with_binary=False), (Results(hr) if streams else None)
 
     def dump_results(self, path):
         """Write the device results of the last run() to a file (the seam between the device pass and the host consumer)."""

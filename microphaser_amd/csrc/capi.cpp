@@ -295,6 +295,30 @@ int mp_batch_results_select(mp_ctx* ctx, mp_batch* batch, uint32_t streams, mp_r
     });
 }
 
+int mp_batch_peptidome(mp_ctx* ctx, mp_batch* batch, uint32_t peptide_len, uint32_t streams, mp_results** results, mp_peptides** out) {
+    PhaseTimer phase_timer("batch_peptidome");
+    return guarded(ctx, [&] {
+        if (!batch->batch.normal) throw Error("mp_batch_peptidome: the batch is a somatic batch - the peptidome is built from a `normal` run (MP_MODE_NORMAL)");
+        check_peptide_len(peptide_len);
+        if (batch->batch.window_len > 0xFFFF) throw Error("mp_batch_peptidome: window length above 65535");
+        DeviceContext& dev = need_device(ctx);
+        if (!batch->ran) throw Error("mp_batch_results before mp_batch_run");
+        if (ctx->last_run != batch) throw Error("mp_batch_results: another batch has been created or run on this context since this one ran - run it again");
+        HostResults hr;
+        dev.download(hr);
+        std::unique_ptr<mp_results> r(new mp_results());
+        PepSources src;
+        consume_batch_normal(batch->batch, hr, r->out, streams, &src);
+        release_later(std::move(hr));
+        std::unique_ptr<mp_peptides> p(new mp_peptides());
+        const RecArena arena{dev.dev_recs(), dev.rec_slots(), dev.rec_stride(), dev.seq_cap()};
+        peptidome_from_sources(dev.device(), src, arena, peptide_len, p->res);   // (the bincode image is built on demand: mp_peptides_binary)
+        release_later(std::move(src));
+        *out = p.release();
+        if (results) *results = r.release();
+    });
+}
+
 void mp_batch_free(mp_batch* batch) { delete batch; }   // (a context never dereferences its resident / last_run pointers)
 
 namespace {

@@ -6,6 +6,9 @@
 // Extra (not in the reference): --device N, or --devices a,b,... = genes sharded over several GPUs from this one process
 // (one context + host thread per GPU; the genes are dealt to the GPUs by estimated cost - longest processing time first on
 // coding nt x depth - and the shards' outputs are merged back into GTF order: byte-identical to one GPU).
+// Extra: `normal ... --peptidome-output peptides.bin [-l/--peptide-length 9]` = `normal | build_reference -o peptides.bin -l 9` in one
+// step: the records are translated where they lie in device memory (mp_batch_peptidome), no nucleotide FASTA is written (stdout stays
+// empty) and the TSV only if --tsv is given; with --devices the shards' peptidomes are joined by mp_peptides_union.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -121,6 +124,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     // microphaser normal <normal.bam> --ref F --variants V [--tsv info.tsv] [-w 27] < gtf > fasta   (src/germline_cli.yaml, src/main.rs:104-143)
+    //             [--peptidome-output peptides.bin [-l 9]]   (the build_reference set of that FASTA instead of the FASTA)
     const bool normal_mode = sub == "normal";
     if (sub != "somatic" && !normal_mode) {
         std::fprintf(stderr, "microphaser (MI355X build): sub-command `%s` is not accelerated in this build; only `somatic`, `normal`, `build_reference` and `filter` are available\n", sub.c_str());
@@ -130,6 +134,9 @@ int main(int argc, char** argv) {
     unsigned long long window_len = 27;
     int warn_only = 0, device = 0;
     std::vector<int> devices;
+    std::string pep_out;
+    unsigned long peptide_len = 9;
+    bool have_len = false, tsv_given = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* {
@@ -138,8 +145,11 @@ int main(int argc, char** argv) {
         };
         if (a == "--variants" || a == "-b") vcf = val();
         else if (a == "--ref" || a == "-r") ref = val();
-        else if (a == "--tsv" || a == "-t") tsv = val();
+        else if (a == "--tsv" || a == "-t") { tsv = val(); tsv_given = true; }
         else if (!normal_mode && (a == "--normal-output" || a == "-n")) normal = val();
+        else if (a == "--peptidome-output") pep_out = val();
+        else if (a == "--peptide-length" || a == "-l") { peptide_len = std::strtoul(val(), nullptr, 10); have_len = true; }
+        else if (a.rfind("-l", 0) == 0 && a.size() > 2) { peptide_len = std::strtoul(a.c_str() + 2, nullptr, 10); have_len = true; }
         else if (a == "--window-len" || a == "-w") window_len = std::strtoull(val(), nullptr, 10);
         else if (a == "--unsupported-allele-warning-only" || a == "-u") warn_only = 1;
         else if (a == "--device") device = std::atoi(val());
@@ -157,6 +167,11 @@ int main(int argc, char** argv) {
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 1; }
     }
     if (bam.empty() || vcf.empty() || ref.empty()) { std::fprintf(stderr, "the sample BAM, --variants and --ref are required\n"); return 1; }
+    if (!pep_out.empty() && !normal_mode) { std::fprintf(stderr, "--peptidome-output is a `normal` option (the germline peptidome)\n"); return 1; }
+    if (have_len && pep_out.empty()) { std::fprintf(stderr, "--peptide-length / -l needs --peptidome-output\n"); return 1; }
+    if (peptide_len < 1 || peptide_len > 25) { std::fprintf(stderr, "--peptide-length / -l must be 1..25\n"); return 1; }
+    const bool pep_mode = !pep_out.empty();
+    const uint32_t pep_streams = tsv_given ? MP_STREAM_TSV : 0;   // (with --peptidome-output the TSV is written only when asked for)
     if (devices.size() == 1) device = devices[0];
     mp_ctx* ctx = nullptr;
     if (mp_create(devices.size() > 1 ? -1 : device, &ctx) != 0) { int rc = fail(ctx, "mp_create"); mp_destroy(ctx); return rc; }   // -1: host-only loader
@@ -186,7 +201,7 @@ int main(int argc, char** argv) {
             for (uint32_t g : order) { Load l = pq.top(); pq.pop(); deal[l.second].push_back(g); pq.push(Load(l.first + cost[g], l.second)); }
             for (auto& v : deal) std::sort(v.begin(), v.end());
         }
-        struct Shard { mp_ctx* ctx = nullptr; mp_results* res = nullptr; std::string err; };
+        struct Shard { mp_ctx* ctx = nullptr; mp_results* res = nullptr; mp_peptides* pep = nullptr; std::string err; };
         std::vector<Shard> shards(nd);
         std::vector<std::thread> th;
         for (size_t k = 0; k < nd; k++)
@@ -194,13 +209,19 @@ int main(int argc, char** argv) {
                 Shard& sh = shards[k];
                 mp_batch* b = nullptr;
                 if (mp_create(devices[k], &sh.ctx) != 0 || mp_batch_create_genes(sh.ctx, ds, mode, window_len, deal[k].data(), uint32_t(deal[k].size()), &b) != 0 ||
-                    mp_batch_run(sh.ctx, b, nullptr) != 0 || mp_batch_results(sh.ctx, b, &sh.res) != 0)
+                    mp_batch_run(sh.ctx, b, nullptr) != 0 ||
+                    (pep_mode ? mp_batch_peptidome(sh.ctx, b, uint32_t(peptide_len), pep_streams, &sh.res, &sh.pep) : mp_batch_results(sh.ctx, b, &sh.res)) != 0)
                     sh.err = sh.ctx ? mp_last_error(sh.ctx) : "mp_create failed";
                 if (b) mp_batch_free(b);
             });
         for (auto& t : th) t.join();
         auto release = [&] {
-            for (Shard& sh : shards) { if (sh.res) mp_results_free(sh.res); if (sh.ctx) mp_destroy(sh.ctx); sh.res = nullptr; sh.ctx = nullptr; }
+            for (Shard& sh : shards) {
+                if (sh.res) mp_results_free(sh.res);
+                if (sh.pep) mp_peptides_free(sh.pep);
+                if (sh.ctx) mp_destroy(sh.ctx);
+                sh.res = nullptr; sh.pep = nullptr; sh.ctx = nullptr;
+            }
             mp_dataset_free(ds);
             mp_destroy(ctx);
         };
@@ -235,6 +256,20 @@ int main(int argc, char** argv) {
             if (!any) streams[2].clear();
         }
         int rc = 0;
+        if (pep_mode) {   // the union of the shards' sorted distinct keys = the peptidome of the whole FASTA
+            std::vector<const uint64_t*> keys(nd);
+            std::vector<uint64_t> counts(nd);
+            for (size_t k = 0; k < nd; k++) { size_t n = 0; keys[k] = mp_peptides_keys(shards[k].pep, &n); counts[k] = n; }
+            mp_peptides* all = nullptr;
+            if (mp_peptides_union(ctx, keys.data(), counts.data(), uint32_t(nd), uint32_t(peptide_len), &all) != 0) { rc = fail(ctx, "microphaser"); release(); return rc; }
+            size_t n = 0;
+            const char* p = mp_peptides_binary(all, &n);
+            if (!write_file(pep_out, p, n)) { std::fprintf(stderr, "cannot write %s\n", pep_out.c_str()); rc = 1; }
+            mp_peptides_free(all);
+            if (!rc && tsv_given && !write_file(tsv, streams[2].data(), streams[2].size())) { std::fprintf(stderr, "cannot write %s\n", tsv.c_str()); rc = 1; }
+            release();
+            return rc;
+        }
         if (!write_stdout(streams[0].data(), streams[0].size())) { std::fprintf(stderr, "cannot write the FASTA records to stdout\n"); rc = 1; }
         if (!rc && !normal_mode && !write_file(normal, streams[1].data(), streams[1].size())) { std::fprintf(stderr, "cannot write %s\n", normal.c_str()); rc = 1; }
         if (!rc && !write_file(tsv, streams[2].data(), streams[2].size())) { std::fprintf(stderr, "cannot write %s\n", tsv.c_str()); rc = 1; }
@@ -243,6 +278,27 @@ int main(int argc, char** argv) {
     }
     mp_results* res = nullptr;
     mp_batch* batch = nullptr;
+    if (pep_mode) {
+        mp_peptides* pep = nullptr;
+        if (mp_batch_create(ctx, ds, mode, window_len, 0, mp_dataset_num_genes(ds), &batch) != 0 || mp_batch_run(ctx, batch, nullptr) != 0 ||
+            mp_batch_peptidome(ctx, batch, uint32_t(peptide_len), pep_streams, &res, &pep) != 0) {
+            int rc = fail(ctx, "microphaser");
+            mp_batch_free(batch); mp_dataset_free(ds); mp_destroy(ctx);
+            return rc;
+        }
+        int rc = 0;
+        size_t n = 0;
+        const char* p = mp_peptides_binary(pep, &n);
+        if (!write_file(pep_out, p, n)) { std::fprintf(stderr, "cannot write %s\n", pep_out.c_str()); rc = 1; }
+        p = mp_results_tsv(res, &n);
+        if (!rc && tsv_given && !write_file(tsv, p, n)) { std::fprintf(stderr, "cannot write %s\n", tsv.c_str()); rc = 1; }
+        mp_peptides_free(pep);
+        mp_results_free(res);
+        mp_batch_free(batch);
+        mp_dataset_free(ds);
+        mp_destroy(ctx);
+        return rc;
+    }
     if (mp_batch_create(ctx, ds, mode, window_len, 0, mp_dataset_num_genes(ds), &batch) != 0 || mp_batch_run(ctx, batch, nullptr) != 0 ||
         mp_batch_results(ctx, batch, &res) != 0) {
         int rc = fail(ctx, "microphaser");

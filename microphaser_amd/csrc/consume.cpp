@@ -614,6 +614,24 @@ void nrecord_add_freq(NormalRecord& r, double freq) {
     r.freq = r.freq + freq;
 }
 
+// The `normal` consumer's output for one gene range: the text streams and, for a fused peptidome (mp_batch_peptidome), one PepSource
+// per record the FASTA stream holds - or would hold, whether or not its text is written.
+struct NormalPart : NormalText {
+    bool want_sources = false;
+    std::vector<PepSource> src;
+    std::vector<uint8_t> merge;   // the sequences of the merged records, window_len bytes each
+    void add_record(uint64_t slot, uint64_t off, uint64_t len, bool rev) {   // bytes [off, off + len) of the device record `slot`
+        if (slot > 0xFFFFFFFFull || off > 0xFF || len > 0xFFFF) throw Error("internal error: record outside the peptide source range");
+        src.push_back(PepSource{uint32_t(slot), uint8_t(off), uint8_t(rev ? SRC_REV : 0), uint16_t(len)});
+    }
+    void add_merged(const uint8_t* seq, uint64_t window_len, char id_last) {   // a splice-side merge's record, built on the host
+        const uint64_t k = window_len ? merge.size() / window_len : 0;
+        if (k > 0xFFFFFFFFull || window_len > 0xFFFF) throw Error("internal error: merged record outside the peptide source range");
+        merge.insert(merge.end(), seq, seq + window_len);
+        src.push_back(PepSource{uint32_t(k), 0, uint8_t(SRC_MERGE | (id_last == 'F' ? 0 : SRC_REV)), uint16_t(window_len)});
+    }
+};
+
 struct NormalConsumerHooks {
     static constexpr bool kNormal = true;
     const Batch& b;
@@ -622,7 +640,7 @@ struct NormalConsumerHooks {
     const Gene& gene;
     const Transcript& transcript;
     const TxDev& T;
-    NormalText& out;
+    NormalPart& out;
     uint64_t window_len;
     size_t next_step = 0, cur_step = 0;
     bool is_fwd;
@@ -777,9 +795,11 @@ struct NormalConsumerHooks {
                     if (splice_pos == 1) {
                         if (splice_gap > seq_len) throw Error("reference would panic: slice index out of range");
                         if (out.streams & STREAM_FASTA) put_fasta(out.fasta, idstr, rseq + splice_gap, seq_len - splice_gap);
+                        if (out.want_sources) out.add_record(gs.rec, splice_gap, seq_len - splice_gap, strand[0] != 'F');
                     } else if (splice_pos == 0) {
                         if (wl > seq_len) throw Error("reference would panic: slice index out of range");
                         if (out.streams & STREAM_FASTA) put_fasta(out.fasta, idstr, rseq, size_t(wl));
+                        if (out.want_sources) out.add_record(gs.rec, 0, wl, strand[0] != 'F');
                     }
                     if (out.streams & STREAM_TSV) {
                         build_lists(variants, ncols, rec, prof_som, L);
@@ -857,6 +877,7 @@ struct NormalConsumerHooks {
                 haplotype_id_into(rec.id, out_seq.data(), out_seq.size(), rec.transcript, kv.first.first, rec.strand.empty() ? '?' : rec.strand[0]);
                 if (out_seq.size() < window_len) throw Error("reference would panic: slice index out of range");
                 if (out.streams & STREAM_FASTA) put_fasta(out.fasta, kv.second.id, out_seq.data(), size_t(window_len));
+                if (out.want_sources) out.add_merged(out_seq.data(), window_len, kv.second.id.back());
                 put_normal_tsv_row(out, kv.second);
             }
         }
@@ -873,6 +894,10 @@ void reserve_streams(NormalText& p, size_t recs) {
     if (p.streams & STREAM_TSV) p.tsv.reserve(recs * 320);
     if (p.streams & STREAM_FASTA) p.fasta.reserve(recs * 56);
     advise_huge(p.tsv.data(), p.tsv.capacity()); advise_huge(p.fasta.data(), p.fasta.capacity());
+}
+void reserve_streams(NormalPart& p, size_t recs) {
+    reserve_streams(static_cast<NormalText&>(p), recs);
+    if (p.want_sources) p.src.reserve(recs);
 }
 const TextBuf* normal_stream(const SomaticText& p) { return &p.normal_fasta; }
 const TextBuf* normal_stream(const NormalText&) { return nullptr; }
@@ -972,15 +997,52 @@ void assemble(std::vector<Out>& parts, PhasedStreams& out, size_t nthreads) {
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_release).count());
 }
 
+inline void want_sources(SomaticText&, bool) {}
+inline void want_sources(NormalPart& p, bool on) { p.want_sources = on; }
+inline void gather_sources(std::vector<SomaticText>&, PepSources*, uint64_t, size_t) {}
+// the parts' sources, concatenated in gene order (merge indices re-based onto the joined merge buffer), on all host threads
+void gather_sources(std::vector<NormalPart>& parts, PepSources* S, uint64_t window_len, size_t nthreads) {
+    if (!S) return;
+    const size_t np = parts.size();
+    std::vector<size_t> s_at(np + 1, 0), m_at(np + 1, 0);
+    for (size_t t = 0; t < np; t++) { s_at[t + 1] = s_at[t] + parts[t].src.size(); m_at[t + 1] = m_at[t] + parts[t].merge.size(); }
+    S->merge_len = uint32_t(window_len);
+    S->n_merge = window_len ? m_at[np] / window_len : 0;
+    if (S->n_merge > 0xFFFFFFFFull) throw Error("internal error: too many merged records for the peptide sources");
+    S->src.resize(s_at[np]);
+    S->merge.resize(m_at[np]);
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t t; (t = next.fetch_add(1)) < np;) {
+            NormalPart& P = parts[t];
+            const uint32_t base = uint32_t(window_len ? m_at[t] / window_len : 0);
+            PepSource* d = S->src.data() + s_at[t];
+            for (size_t i = 0; i < P.src.size(); i++) {
+                d[i] = P.src[i];
+                if (d[i].flags & SRC_MERGE) d[i].idx += base;
+            }
+            if (!P.merge.empty()) std::memcpy(S->merge.data() + m_at[t], P.merge.data(), P.merge.size());
+            std::vector<PepSource>().swap(P.src);
+            std::vector<uint8_t>().swap(P.merge);
+        }
+    };
+    std::vector<std::thread> th;
+    for (size_t k = 1; k < std::max<size_t>(1, std::min(nthreads, np)); k++) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+}
+
 template <class Hooks, class Out>
-void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams) {
+void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams, PepSources* sources) {
     size_t nthreads = host_threads();
     const size_t ng = b.genes.size();
     if (nthreads > ng) nthreads = ng ? ng : 1;
     if (nthreads <= 1) {
         std::vector<Out> one(1);
         one[0].streams = streams;
+        want_sources(one[0], sources != nullptr);
         consume_range<Hooks>(b, res, 0, ng, one[0]);
+        gather_sources(one, sources, b.window_len, 1);
         assemble(one, out, 1);
         return;
     }
@@ -1001,7 +1063,7 @@ void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out,
     }
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<Out> parts(nthreads);
-    for (Out& p : parts) p.streams = streams;
+    for (Out& p : parts) { p.streams = streams; want_sources(p, sources != nullptr); }
     std::vector<std::string> errors(nthreads);
     std::vector<std::thread> th;
     // Reserve each range's streams up front (an estimate from the records the device produced, shared out by planned steps; pages
@@ -1020,6 +1082,7 @@ void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out,
     for (auto& x : th) x.join();
     for (size_t t = 0; t < nthreads; t++)
         if (!errors[t].empty()) throw Error(errors[t]);  // the first failing gene range in gene order, like a sequential run
+    gather_sources(parts, sources, b.window_len, nthreads);
     const auto t1 = std::chrono::steady_clock::now();
     assemble(parts, out, nthreads);
     if (std::getenv("MP_DEBUG"))
@@ -1031,12 +1094,12 @@ void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out,
 
 void consume_batch(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams) {
     if (b.normal) throw Error("internal error: somatic consumer on a normal-mode batch");
-    consume_sharded<ConsumerHooks, SomaticText>(b, res, out, streams);
+    consume_sharded<ConsumerHooks, SomaticText>(b, res, out, streams, nullptr);
 }
 
-void consume_batch_normal(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams) {
+void consume_batch_normal(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams, PepSources* sources) {
     if (!b.normal) throw Error("internal error: normal consumer on a somatic-mode batch");
-    consume_sharded<NormalConsumerHooks, NormalText>(b, res, out, streams);
+    consume_sharded<NormalConsumerHooks, NormalPart>(b, res, out, streams, sources);
 }
 
 }  // namespace mp

@@ -2,6 +2,7 @@
 #pragma once
 #include "batch.hpp"
 #include "device.hpp"
+#include "pep.hpp"
 
 namespace mp {
 
@@ -12,7 +13,8 @@ namespace mp {
 void consume_batch(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams = STREAM_ALL);
 
 // The same for `microphaser normal` (reference: src/normal_microphasing.rs:650-1279); the batch must have been planned
-// with normal = true.
-void consume_batch_normal(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams = STREAM_ALL);
+// with normal = true. sources != nullptr: also one PepSource per record of the FASTA stream (whether or not its text is asked for),
+// in gene order - what peptidome_from_sources translates.
+void consume_batch_normal(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams = STREAM_ALL, PepSources* sources = nullptr);
 
 }  // namespace mp

@@ -53,6 +53,12 @@ class DeviceContext {
     void free_batch();
     int device() const { return device_; }
     uint64_t hbm_bytes() const { return hbm_bytes_; }
+    // the record arena of the resident batch (slot i at recs + i * rec_stride, the index GroupSum::rec holds): read in place by the
+    // fused `normal` peptidome
+    const uint8_t* dev_recs() const { return d_.recs; }
+    uint64_t rec_slots() const { return rec_cap_; }
+    uint32_t rec_stride() const { return d_.rec_stride; }
+    uint32_t seq_cap() const { return d_.seq_cap; }
 
   private:
     // Host <-> device transfers go through a small ring of PINNED staging buffers (f1; the reference side is the per-gene

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <sstream>
 #include <thread>
@@ -40,6 +42,28 @@ std::string PeptideResult::binary() const {
     for (size_t i = 0; i < n; i++) { u64(peptide_len); b += peptide_from_key(key_at(keys.data(), i, w), peptide_len); }
     return b;
 }
+
+namespace {
+const char* const BAD_CODON = "reference would panic: called `Result::unwrap()` on an `Err` value (codon with a base other than A, C, G, T)";
+
+// The de-duplication both peptidome paths end in: sort + unique of the n translated keys in d_keys (d_tmp, d_out: scratch of the same
+// size) after e1, the distinct keys into out.keys and the event times into out. Returns the translation's error flag (the caller frees
+// its buffers, then throws BAD_CODON).
+uint32_t dedup_keys(uint64_t* d_keys, uint64_t* d_tmp, uint64_t* d_out, const uint32_t* d_err, uint64_t n, hipStream_t stream, hipEvent_t e0,
+                    hipEvent_t e1, hipEvent_t e2, PeptideResult& out) {
+    const uint32_t L = out.peptide_len, w = key_words(L);
+    const uint64_t nu = device_sort_unique(d_keys, d_tmp, d_out, n, L, stream);
+    HIP_OK(hipEventRecord(e2, stream));
+    uint32_t err = 0;
+    out.keys.resize(nu * w);
+    HIP_OK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, stream));
+    if (nu) HIP_OK(hipMemcpyAsync(out.keys.data(), d_out, nu * w * 8, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipEventElapsedTime(&out.translate_ms, e0, e1));
+    HIP_OK(hipEventElapsedTime(&out.dedup_ms, e1, e2));
+    return err;
+}
+}  // namespace
 
 void build_reference_device(int device, std::string_view fasta_text, uint32_t L, PeptideResult& out, bool want_fasta) {
     check_peptide_len(L);
@@ -162,18 +186,10 @@ void build_reference_device(int device, std::string_view fasta_text, uint32_t L,
         HIP_OK(hipEventRecord(e0, stream));
         device_translate(d_nt, d_off, d_rev, n, L, d_aa, d_keys, d_err, stream);
         HIP_OK(hipEventRecord(e1, stream));
-        uint64_t nu = device_sort_unique(d_keys, d_tmp, d_out, n, L, stream);
-        HIP_OK(hipEventRecord(e2, stream));
-        uint32_t err = 0;
-        out.keys.resize(nu * w);
-        HIP_OK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, stream));
         if (want_fasta) HIP_OK(hipMemcpyAsync(aa.data(), d_aa, n * L, hipMemcpyDeviceToHost, stream));
-        if (nu) HIP_OK(hipMemcpyAsync(out.keys.data(), d_out, nu * w * 8, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(hipEventElapsedTime(&out.translate_ms, e0, e1));
-        HIP_OK(hipEventElapsedTime(&out.dedup_ms, e1, e2));
+        const uint32_t err = dedup_keys(d_keys, d_tmp, d_out, d_err, n, stream, e0, e1, e2, out);
         for (void* p : {(void*)d_nt, (void*)d_rev, (void*)d_aa, (void*)d_off, (void*)d_keys, (void*)d_tmp, (void*)d_out, (void*)d_err}) hipFree(p);
-        if (err) throw Error("reference would panic: called `Result::unwrap()` on an `Err` value (codon with a base other than A, C, G, T)");
+        if (err) throw Error(BAD_CODON);
     }
     hipEventDestroy(e0); hipEventDestroy(e1); hipEventDestroy(e2);
     hipStreamDestroy(stream);
@@ -192,6 +208,67 @@ void build_reference_device(int device, std::string_view fasta_text, uint32_t L,
                 out.fasta.push_back('\n');
             }
     }
+}
+
+}  // namespace mp
+
+namespace mp {
+
+void peptidome_from_sources(int device, const PepSources& S, const RecArena& arena, uint32_t L, PeptideResult& out) {
+    check_peptide_len(L);
+    const uint32_t w = key_words(L);
+    out = PeptideResult();
+    out.peptide_len = L;
+    // every source must lie inside what it names: the kernel reads [off, off + len) of a record's sequence or one merge sequence
+    const uint64_t n_src = S.src.size();
+    uint64_t n = 0;
+    for (const PepSource& ps : S.src) {
+        const bool ok = (ps.flags & SRC_MERGE) ? (ps.idx < S.n_merge && ps.len == S.merge_len)
+                                               : (ps.idx < arena.n_slots && uint32_t(ps.off) + ps.len <= arena.seq_cap);
+        if (!ok) throw Error("internal error: peptide source outside the record arena");
+        n += source_windows(ps.len, L);
+    }
+    if (S.merge.size() != S.n_merge * S.merge_len) throw Error("internal error: merge buffer size");
+    out.n_peptides = n;
+    if (!n) return;
+    if (!arena.recs) throw Error("internal error: no device record arena");
+    HIP_OK(hipSetDevice(device));
+    hipStream_t stream;
+    HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    hipEvent_t e0, e1, e2;
+    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2));
+    PepSource* d_src = nullptr;
+    uint8_t* d_merge = nullptr;
+    uint64_t *d_win_at = nullptr, *d_keys = nullptr, *d_tmp = nullptr, *d_out = nullptr;
+    uint32_t* d_err = nullptr;
+    uint32_t err = 0;
+    auto release = [&] {
+        for (void* p : {(void*)d_src, (void*)d_merge, (void*)d_win_at, (void*)d_keys, (void*)d_tmp, (void*)d_out, (void*)d_err}) (void)hipFree(p);
+        hipEventDestroy(e0); hipEventDestroy(e1); hipEventDestroy(e2);
+        hipStreamDestroy(stream);
+    };
+    try {
+        HIP_OK(hipMalloc(&d_src, n_src * sizeof(PepSource))); HIP_OK(hipMalloc(&d_win_at, n_src * 8));
+        if (!S.merge.empty()) HIP_OK(hipMalloc(&d_merge, S.merge.size()));
+        HIP_OK(hipMalloc(&d_keys, n * w * 8)); HIP_OK(hipMalloc(&d_tmp, n * w * 8)); HIP_OK(hipMalloc(&d_out, n * w * 8));
+        HIP_OK(hipMalloc(&d_err, 4));
+        HIP_OK(hipMemcpyAsync(d_src, S.src.data(), n_src * sizeof(PepSource), hipMemcpyHostToDevice, stream));
+        if (!S.merge.empty()) HIP_OK(hipMemcpyAsync(d_merge, S.merge.data(), S.merge.size(), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemsetAsync(d_err, 0, 4, stream));
+        HIP_OK(hipEventRecord(e0, stream));
+        device_translate_sources(d_src, d_win_at, n_src, n, arena.recs, arena.rec_stride, d_merge, S.merge_len, L, d_keys, d_err, stream);
+        HIP_OK(hipEventRecord(e1, stream));
+        err = dedup_keys(d_keys, d_tmp, d_out, d_err, n, stream, e0, e1, e2, out);
+    } catch (...) {
+        release();
+        throw;
+    }
+    release();
+    if (std::getenv("MP_DEBUG"))
+        std::fprintf(stderr, "[mp]   peptidome from %llu sources (%llu B) + %llu merged records (%llu B): %llu windows, translate %.3f ms, dedup %.3f ms\n",
+                     (unsigned long long)n_src, (unsigned long long)(n_src * sizeof(PepSource)), (unsigned long long)S.n_merge,
+                     (unsigned long long)S.merge.size(), (unsigned long long)n, out.translate_ms, out.dedup_ms);
+    if (err) throw Error(BAD_CODON);
 }
 
 }  // namespace mp

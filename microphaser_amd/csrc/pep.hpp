@@ -43,4 +43,32 @@ struct PeptideResult {
 // want_fasta = false: the peptidome (keys, binary) only - what a pipeline that feeds `filter` needs; the translated FASTA stays empty.
 void build_reference_device(int device, std::string_view fasta_text, uint32_t peptide_len, PeptideResult& out, bool want_fasta = true);   // (the text is read in place)
 
+// ---- `normal` -> `build_reference` without the FASTA text: one source per record the `normal` consumer would print
+// (consume.cpp), translated straight from the device record arena (kernels_pep.hip k4_translate_sources).
+enum : uint8_t { SRC_REV = 1, SRC_MERGE = 2 };
+struct PepSource {       // 8 bytes; 100 M of them stand in for ~5 GB of FASTA text
+    uint32_t idx;        // SRC_MERGE clear: record slot in the device arena (GroupSum::rec); set: index of a window_len-byte sequence in the merge buffer
+    uint8_t off;         // first base within the record's sequence (device records only)
+    uint8_t flags;       // SRC_REV: reverse-complement (the printed id does not end in 'F', src/peptides.rs:161-164)
+    uint16_t len;        // bases
+};
+static_assert(sizeof(PepSource) == 8, "PepSource layout");
+// windows of a record of `len` bases: peptides::build's `while i + 3L <= len` loop, step 3 (src/peptides.rs:165-174)
+inline uint64_t source_windows(uint64_t len, uint32_t L) { return len >= 3ull * L ? (len - 3ull * L) / 3 + 1 : 0; }
+struct PepSources {      // the records of a batch in gene order, and the host-built sequences of its splice-side merges
+    PodVec<PepSource> src;
+    PodVec<uint8_t> merge;        // n_merge * merge_len bytes
+    uint32_t merge_len = 0;       // the batch's window length
+    uint64_t n_merge = 0;
+};
+// The device arena the sources name: record i's sequence starts at recs + i * rec_stride + 32 (HapRecHdr), seq_cap bytes at most.
+struct RecArena {
+    const uint8_t* recs = nullptr;
+    uint64_t n_slots = 0;
+    uint32_t rec_stride = 0, seq_cap = 0;
+};
+// Translate every window of every source and de-duplicate on HIP device `device` (the one that holds the arena): the keys, count and
+// bincode image build_reference_device gives on the FASTA those records would have been printed as.
+void peptidome_from_sources(int device, const PepSources& s, const RecArena& arena, uint32_t peptide_len, PeptideResult& out);
+
 }  // namespace mp

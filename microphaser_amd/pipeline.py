@@ -16,10 +16,15 @@ from . import MODE_NORMAL, MODE_SOMATIC, STREAM_FASTA
 from .shard import gather_shards, merge_by_gene, shard_of, union_keys
 
 
-def normal_peptidome_keys(ctx, ds, local_genes, peptide_len):
-    """This rank's share of the normal peptidome: `normal` on its genes, every window translated and de-duplicated on the GPU."""
+def normal_peptidome_keys(ctx, ds, local_genes, peptide_len, fused_peptidome=False):
+    """This rank's share of the normal peptidome: `normal` on its genes, every window translated and de-duplicated on the GPU.
+    fused_peptidome: translate the records where they lie in device memory (Batch.peptidome) instead of going through the
+    nucleotide FASTA text; the same keys, and no Results (None)."""
     nb = ds.batch_genes(local_genes, window_len=3 * peptide_len, mode=MODE_NORMAL)
     nb.run()
+    if fused_peptidome:
+        pep, _ = nb.peptidome(peptide_len)
+        return pep.keys_np, None
     nres = nb.results(STREAM_FASTA)                # build_reference reads the FASTA only: the TSV text is not produced
     pep = ctx.peptidome(nres.fasta, peptide_len)   # keys only (no translated FASTA text)
     return pep.keys_np, nres
@@ -31,11 +36,11 @@ def somatic_shard(ds, local_genes, global_genes, peptide_len):
     return shard_of(sb.results(), global_genes)
 
 
-def config_e_rank(ctx, ds, local_genes, global_genes, peptide_len=9, dist=None, device="cpu"):
+def config_e_rank(ctx, ds, local_genes, global_genes, peptide_len=9, dist=None, device="cpu", fused_peptidome=False):
     """One rank of config E. ds holds (at least) this rank's genes; local_genes are their ordinals in ds, global_genes their
     ordinals in the whole exome (the merge key). Returns (merged somatic streams, peptidome, filter result) on rank 0 and
-    (None, peptidome, None) elsewhere."""
-    keys, _ = normal_peptidome_keys(ctx, ds, local_genes, peptide_len)
+    (None, peptidome, None) elsewhere. fused_peptidome: see normal_peptidome_keys."""
+    keys, _ = normal_peptidome_keys(ctx, ds, local_genes, peptide_len, fused_peptidome)
     peptidome = union_keys(ctx, keys, peptide_len, dist, device)          # the same on every rank
     shard = somatic_shard(ds, local_genes, global_genes, peptide_len)
     shards = gather_shards(shard, dist, dst=0, device=device)

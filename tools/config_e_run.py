@@ -8,7 +8,10 @@ so the exome is walked in gene chunks - exactly what the ranks of a multi-GPU ru
 per chunk normal -> FASTA -> build_reference -> sorted distinct keys; the chunks' key arrays are merged by mp_peptides_union; then
 `somatic` per chunk, shards merged by gene, and one `filter` over the merged TSV.
 
-  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--peptide-len 9] [--out config_e.json]
+  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--peptide-len 9] [--fused-peptidome] [--out config_e.json]
+
+(--fused-peptidome: per chunk `normal` -> Batch.peptidome, the records translated where they lie in device memory, no nucleotide
+FASTA; normal_s then includes the peptidome, build_reference_s is 0, and wall_s["fused_peptidome_s"] is the peptidome call alone)
 
 (--peptide-len L: windows of 3L nt in `normal` and `somatic`; 13..25 are the MHC class II lengths, with two-word peptide keys)
 """
@@ -26,13 +29,15 @@ import microphaser_amd as m
 from microphaser_amd.shard import merge_by_gene, shard_of
 
 
-def phased(ds, genes, window_len, mode, streams, skip_panics, skipped):
+def phased(ds, genes, window_len, mode, streams, skip_panics, skipped, take=None):
     """(genes, RunStats, Results) of one batch of `genes`; with skip_panics, a batch that holds a gene the reference would panic on
-    (the oracle's --skip-panics) is phased gene by gene instead, that gene left out and recorded in `skipped`."""
+    (the oracle's --skip-panics) is phased gene by gene instead, that gene left out and recorded in `skipped`. take(batch): what to
+    return in place of the Results (default: batch.results(streams))."""
+    take = take or (lambda b: b.results(streams))
     try:
         b = ds.batch_genes(genes, window_len=window_len, mode=mode)
         st = b.run()
-        return [(genes, st, b.results(streams))]
+        return [(genes, st, take(b))]
     except m.MicrophaserError as e:
         if not (skip_panics and str(e).startswith("reference would panic")):
             raise
@@ -41,7 +46,7 @@ def phased(ds, genes, window_len, mode, streams, skip_panics, skipped):
         try:
             b = ds.batch_genes([g], window_len=window_len, mode=mode)
             st = b.run()
-            out.append(([g], st, b.results(streams)))
+            out.append(([g], st, take(b)))
         except m.MicrophaserError as e:
             if not str(e).startswith("reference would panic"):
                 raise
@@ -55,6 +60,7 @@ def main():
     ap.add_argument("--chunks", type=int, default=8)
     ap.add_argument("--peptide-len", type=int, default=9)
     ap.add_argument("--skip-panics", action="store_true", help="leave out genes the reference would panic on (phased gene by gene)")
+    ap.add_argument("--fused-peptidome", action="store_true", help="normal -> peptidome on the device (Batch.peptidome), no nucleotide FASTA")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     L = a.peptide_len
@@ -68,10 +74,24 @@ def main():
     stats = dict(normal_windows=0, normal_fasta_bytes=0, normal_tsv_bytes=0, k2n_ms=0.0, k3_ms=0.0, k3b_ms=0.0, k1_ms=0.0, peptide_windows=0)
     key_arrays = []
     skipped = {"normal": [], "somatic": []}
-    t_normal = t_build = 0.0
+    t_normal = t_build = t_fused = 0.0
     for c in range(a.chunks):
         genes = list(range(cuts[c], cuts[c + 1]))
         t0 = time.perf_counter()
+        if a.fused_peptidome:
+            def fused(b):
+                tp = time.perf_counter()
+                pep, _ = b.peptidome(L)
+                return pep, time.perf_counter() - tp
+            for _g, st, (pep, dt) in phased(ds, genes, 3 * L, m.MODE_NORMAL, 0, a.skip_panics, skipped["normal"], take=fused):
+                stats["k1_ms"] += st.k1_ms; stats["k2n_ms"] += st.k2seq_ms; stats["k3_ms"] += st.k3_ms; stats["k3b_ms"] += st.k3b_ms
+                stats["peptide_windows"] += pep.count
+                key_arrays.append(pep.keys_np)
+                t_fused += dt
+                pep.close()
+            t_normal += time.perf_counter() - t0
+            print("chunk %d/%d: normal + fused peptidome %.1f s so far" % (c + 1, a.chunks, t_normal), flush=True)
+            continue
         parts = []
         for _g, st, res in phased(ds, genes, 3 * L, m.MODE_NORMAL, m.STREAM_FASTA, a.skip_panics, skipped["normal"]):
             parts.append(res.fasta)           # build_reference reads the FASTA only
@@ -91,6 +111,8 @@ def main():
         t_build += time.perf_counter() - t0
         print("chunk %d/%d: normal %.1f s, build_reference %.1f s so far" % (c + 1, a.chunks, t_normal, t_build), flush=True)
     t["normal_s"], t["build_reference_s"] = t_normal, t_build
+    if a.fused_peptidome:
+        t["fused_peptidome_s"] = t_fused
     t0 = time.perf_counter()
     peptidome = ctx.peptides_union(key_arrays, L)
     t["peptides_union_s"] = time.perf_counter() - t0
@@ -114,8 +136,9 @@ def main():
     f = ctx.filter(merged["tsv"], peptidome)        # the peptidome handle: its keys go to the GPU as they are
     t["filter_s"] = time.perf_counter() - t0
     stats.update(filter_rows=f.rows, filter_kept=f.kept, filter_removed=f.removed, filter_groups=f.groups, skipped_genes=skipped)
-    t["total_s"] = sum(v for k, v in t.items() if k != "generate_s")
-    out = {"config": "E: normal + build_reference -l %d + somatic + filter, %d transcripts, %d gene chunks, one MI355X" % (L, a.transcripts, a.chunks),
+    t["total_s"] = sum(v for k, v in t.items() if k not in ("generate_s", "fused_peptidome_s"))   # (the latter is inside normal_s)
+    out = {"config": "E: normal + build_reference -l %d + somatic + filter, %d transcripts, %d gene chunks, one MI355X%s" %
+                     (L, a.transcripts, a.chunks, ", fused normal -> peptidome" if a.fused_peptidome else ""),
            "wall_s": t, "stats": stats}
     print(json.dumps(out))
     if a.out:
