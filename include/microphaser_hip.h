@@ -243,6 +243,18 @@ int mp_peptides_union(mp_ctx* ctx, const uint64_t* const* keys, const uint64_t* 
 int mp_batch_peptidome(mp_ctx* ctx, mp_batch* batch, uint32_t peptide_len, uint32_t streams, mp_results** results,
                        mp_peptides** out);
 
+typedef struct mp_filtered mp_filtered;
+/* `somatic` -> `filter` without the info.tsv text: the filter of exactly the rows mp_batch_results would write to the TSV stream,
+ * their mutant / normal windows translated on the GPU where they lie in the device-resident haplotype records (reference:
+ * src/microphasing.rs print + merge, src/peptides.rs:221-709). Same five streams, counts and errors as mp_filter_peptides /
+ * mp_filter_buffers on that TSV. mp_batch_filter filters at the peptidome's length; mp_batch_filter_binary takes the bincode
+ * HashSet<Vec<u8>> bytes build_reference -o writes, 1 <= peptide_len <= 25. streams: text streams wanted from the same consumer
+ * pass (0 = none; results may then be NULL). Call after mp_batch_run of a MP_MODE_SOMATIC batch; fails like mp_batch_results if
+ * another batch ran on the context since, and on a host-only context (no CPU fallback). */
+int mp_batch_filter(mp_ctx* ctx, mp_batch* batch, const mp_peptides* reference, uint32_t streams, mp_results** results, mp_filtered** out);
+int mp_batch_filter_binary(mp_ctx* ctx, mp_batch* batch, const char* reference_binary, size_t len, uint32_t peptide_len, uint32_t streams,
+                           mp_results** results, mp_filtered** out);
+
 /* `microphaser filter` (reference: peptides::filter, src/peptides.rs:221-709 <- run_filtering, src/main.rs:170-214,
  * src/filter_cli.yaml): translate the mutant / normal windows of a `somatic` info.tsv, drop self-similar, repeated and
  * post-stop peptides, remove those present in the reference peptidome (bincode HashSet<Vec<u8>> from build_reference)
@@ -251,7 +263,6 @@ int mp_batch_peptidome(mp_ctx* ctx, mp_batch* batch, uint32_t peptide_len, uint3
  * mp_filter reads the two files; mp_filter_buffers takes their bytes (read in place); mp_filter_peptides takes the peptidome as the
  * handle build_reference / mp_peptides_union returned (its sorted keys go to the GPU as they are: no bincode round trip) and
  * filters at that peptidome's peptide length. */
-typedef struct mp_filtered mp_filtered;
 int mp_filter(mp_ctx* ctx, const char* tsv_path, const char* reference_binary_path, uint32_t peptide_len, mp_filtered** out);
 int mp_filter_buffers(mp_ctx* ctx, const char* tsv, size_t tsv_len, const char* reference_binary, size_t reference_len,
                       uint32_t peptide_len, mp_filtered** out);

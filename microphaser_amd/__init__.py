@@ -186,6 +186,8 @@ def lib():
         "mp_batch_results": (i32, [vp, vp, pp]),
         "mp_batch_results_select": (i32, [vp, vp, u32, pp]),
         "mp_batch_peptidome": (i32, [vp, vp, u32, u32, pp, pp]),
+        "mp_batch_filter": (i32, [vp, vp, vp, u32, pp, pp]),
+        "mp_batch_filter_binary": (i32, [vp, vp, cp, ctypes.c_size_t, u32, u32, pp, pp]),
         "mp_batch_free": (None, [vp]),
         "mp_phase_dataset": (i32, [vp, vp, i32, u64, pp]),
         "mp_results_fasta": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
@@ -233,6 +235,7 @@ C_ABI_SYMBOLS = [
     "mp_synth_gene_costs", "mp_dataset_from_arrays", "mp_dataset_to_arrays", "mp_gene_batch_free", "mp_dataset_gene_costs",
     "mp_batch_create_genes", "mp_results_gene_offsets", "mp_translate", "mp_peptides_union", "mp_build_reference_buffer", "mp_peptidome_from_buffer",
     "mp_batch_results_dump", "mp_batch_results_from_dump", "mp_peptides_key_words", "mp_key_words", "mp_batch_peptidome",
+    "mp_batch_filter", "mp_batch_filter_binary",
 ]
 
 
@@ -547,6 +550,21 @@ class Batch:
         self.ctx._check(lib().mp_batch_peptidome(self.ctx._h, self._h, peptide_len, streams, ctypes.byref(hr) if streams else None,
                                                  ctypes.byref(hp)))
         return Peptides(hp, with_binary=False), (Results(hr) if streams else None)
+
+    def filter(self, reference, peptide_len=9, streams=0):
+        """`somatic` -> `filter` in one step (mp_batch_filter / mp_batch_filter_binary): the filter of the rows results() would write to
+        the TSV stream, their windows translated on the GPU where they lie in device memory - no info.tsv in between. reference: a
+        Peptides handle (its peptide length wins over peptide_len) or the bincode bytes build_reference writes. Returns (Filtered,
+        Results of the streams asked for in the same consumer pass, or None when streams == 0)."""
+        hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
+        pr = ctypes.byref(hr) if streams else None
+        if isinstance(reference, Peptides):
+            self.ctx._check(lib().mp_batch_filter(self.ctx._h, self._h, reference._h, streams, pr, ctypes.byref(hf)))
+        else:
+            reference = bytes(reference)
+            self.ctx._check(lib().mp_batch_filter_binary(self.ctx._h, self._h, reference, len(reference), peptide_len, streams, pr,
+                                                         ctypes.byref(hf)))
+        return Filtered(hf), (Results(hr) if streams else None)
 
     def dump_results(self, path):
         """Write the device results of the last run() to a file (the seam between the device pass and the host consumer)."""

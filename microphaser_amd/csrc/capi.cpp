@@ -319,6 +319,53 @@ int mp_batch_peptidome(mp_ctx* ctx, mp_batch* batch, uint32_t peptide_len, uint3
     });
 }
 
+}  // extern "C"
+
+namespace {
+// `somatic` -> `filter` on the resident batch: the consumer captures the rows (and writes the text streams asked for), the filter reads
+// their windows where they lie in device memory. The host copy of the records stays alive until the filter is done: the captured rows'
+// sequence fields point into it.
+void batch_filter(mp_ctx* ctx, mp_batch* batch, const char* what, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys,
+                  uint32_t peptide_len, uint32_t streams, mp_results** results, mp_filtered** out) {
+    if (batch->batch.normal)
+        throw Error(std::string(what) + ": the batch is a normal batch - the filter reads the rows of a `somatic` run (MP_MODE_SOMATIC)");
+    check_peptide_len(peptide_len);
+    DeviceContext& dev = need_device(ctx);
+    if (!batch->ran) throw Error("mp_batch_results before mp_batch_run");
+    if (ctx->last_run != batch) throw Error("mp_batch_results: another batch has been created or run on this context since this one ran - run it again");
+    HostResults hr;
+    dev.download(hr);
+    std::unique_ptr<mp_results> r(new mp_results());
+    RowCapture cap;
+    consume_batch(batch->batch, hr, r->out, streams, &cap);
+    std::unique_ptr<mp_filtered> f(new mp_filtered());
+    const RecArena arena{dev.dev_recs(), dev.rec_slots(), dev.rec_stride(), dev.seq_cap()};
+    filter_captured(dev.device(), reference_binary, reference_keys, cap, arena, peptide_len, f->res);
+    release_later(std::move(cap));
+    release_later(std::move(hr));
+    *out = f.release();
+    if (results) *results = r.release();
+}
+}  // namespace
+
+extern "C" {
+
+int mp_batch_filter(mp_ctx* ctx, mp_batch* batch, const mp_peptides* reference, uint32_t streams, mp_results** results, mp_filtered** out) {
+    PhaseTimer phase_timer("batch_filter");
+    return guarded(ctx, [&] {
+        if (!reference) throw Error("mp_batch_filter: no peptidome");
+        batch_filter(ctx, batch, "mp_batch_filter", std::string_view(), &reference->res.keys, reference->res.peptide_len, streams, results, out);
+    });
+}
+
+int mp_batch_filter_binary(mp_ctx* ctx, mp_batch* batch, const char* reference_binary, size_t len, uint32_t peptide_len, uint32_t streams,
+                           mp_results** results, mp_filtered** out) {
+    PhaseTimer phase_timer("batch_filter");
+    return guarded(ctx, [&] {
+        batch_filter(ctx, batch, "mp_batch_filter_binary", std::string_view(reference_binary, len), nullptr, peptide_len, streams, results, out);
+    });
+}
+
 void mp_batch_free(mp_batch* batch) { delete batch; }   // (a context never dereferences its resident / last_run pointers)
 
 namespace {

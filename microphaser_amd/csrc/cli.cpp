@@ -9,6 +9,10 @@
 // Extra: `normal ... --peptidome-output peptides.bin [-l/--peptide-length 9]` = `normal | build_reference -o peptides.bin -l 9` in one
 // step: the records are translated where they lie in device memory (mp_batch_peptidome), no nucleotide FASTA is written (stdout stays
 // empty) and the TSV only if --tsv is given; with --devices the shards' peptidomes are joined by mp_peptides_union.
+// Extra: `somatic ... --filter-reference peptides.bin [-l 9] [--filtered-tsv info.filtered.tsv] [-s info.removed.tsv]
+// [-p peptides.removed.fasta] [--filtered-normal-output normal.filtered.fa]` = `somatic` then `filter -r peptides.bin` in one step: the
+// rows are filtered where their windows lie in device memory (mp_batch_filter_binary), no info.tsv in between. stdout and the four files
+// are what `filter` writes (same defaults); --tsv and -n/--normal-output write the somatic streams only when given. One GPU.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -136,7 +140,9 @@ int main(int argc, char** argv) {
     std::vector<int> devices;
     std::string pep_out;
     unsigned long peptide_len = 9;
-    bool have_len = false, tsv_given = false;
+    bool have_len = false, tsv_given = false, normal_given = false;
+    std::string filt_ref, f_tsv = "info.filtered.tsv", f_sim = "info.removed.tsv", f_rem = "peptides.removed.fasta", f_norm = "normal.filtered.fa";
+    bool filt_out_given = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* {
@@ -146,8 +152,13 @@ int main(int argc, char** argv) {
         if (a == "--variants" || a == "-b") vcf = val();
         else if (a == "--ref" || a == "-r") ref = val();
         else if (a == "--tsv" || a == "-t") { tsv = val(); tsv_given = true; }
-        else if (!normal_mode && (a == "--normal-output" || a == "-n")) normal = val();
+        else if (!normal_mode && (a == "--normal-output" || a == "-n")) { normal = val(); normal_given = true; }
         else if (a == "--peptidome-output") pep_out = val();
+        else if (a == "--filter-reference") filt_ref = val();
+        else if (a == "--filtered-tsv") { f_tsv = val(); filt_out_given = true; }
+        else if (a == "--similar-removed" || a == "-s") { f_sim = val(); filt_out_given = true; }
+        else if (a == "--removed-peptides" || a == "-p") { f_rem = val(); filt_out_given = true; }
+        else if (a == "--filtered-normal-output") { f_norm = val(); filt_out_given = true; }
         else if (a == "--peptide-length" || a == "-l") { peptide_len = std::strtoul(val(), nullptr, 10); have_len = true; }
         else if (a.rfind("-l", 0) == 0 && a.size() > 2) { peptide_len = std::strtoul(a.c_str() + 2, nullptr, 10); have_len = true; }
         else if (a == "--window-len" || a == "-w") window_len = std::strtoull(val(), nullptr, 10);
@@ -168,8 +179,22 @@ int main(int argc, char** argv) {
     }
     if (bam.empty() || vcf.empty() || ref.empty()) { std::fprintf(stderr, "the sample BAM, --variants and --ref are required\n"); return 1; }
     if (!pep_out.empty() && !normal_mode) { std::fprintf(stderr, "--peptidome-output is a `normal` option (the germline peptidome)\n"); return 1; }
-    if (have_len && pep_out.empty()) { std::fprintf(stderr, "--peptide-length / -l needs --peptidome-output\n"); return 1; }
+    if (!filt_ref.empty() && normal_mode) { std::fprintf(stderr, "--filter-reference is a `somatic` option (the filter of its neopeptides)\n"); return 1; }
+    if (have_len && normal_mode && pep_out.empty()) { std::fprintf(stderr, "--peptide-length / -l needs --peptidome-output\n"); return 1; }
+    if (have_len && !normal_mode && filt_ref.empty()) { std::fprintf(stderr, "--peptide-length / -l on `somatic` needs --filter-reference\n"); return 1; }
+    if (filt_out_given && filt_ref.empty()) { std::fprintf(stderr, "--filtered-tsv / -s / -p / --filtered-normal-output need --filter-reference\n"); return 1; }
     if (peptide_len < 1 || peptide_len > 25) { std::fprintf(stderr, "--peptide-length / -l must be 1..25\n"); return 1; }
+    if (!filt_ref.empty() && devices.size() > 1) { std::fprintf(stderr, "--filter-reference runs on one GPU: --devices names more than one\n"); return 1; }
+    std::string filt_ref_bytes;
+    if (!filt_ref.empty()) {   // (read before any device work: a missing file is an argument error)
+        FILE* f = std::fopen(filt_ref.c_str(), "rb");
+        if (!f) { std::fprintf(stderr, "cannot open %s\n", filt_ref.c_str()); return 1; }
+        char buf[1 << 16];
+        for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) filt_ref_bytes.append(buf, k);
+        const bool bad = std::ferror(f) != 0;
+        std::fclose(f);
+        if (bad) { std::fprintf(stderr, "cannot read %s\n", filt_ref.c_str()); return 1; }
+    }
     const bool pep_mode = !pep_out.empty();
     const uint32_t pep_streams = tsv_given ? MP_STREAM_TSV : 0;   // (with --peptidome-output the TSV is written only when asked for)
     if (devices.size() == 1) device = devices[0];
@@ -278,6 +303,40 @@ int main(int argc, char** argv) {
     }
     mp_results* res = nullptr;
     mp_batch* batch = nullptr;
+    if (!filt_ref.empty()) {
+        const uint32_t streams = (tsv_given ? MP_STREAM_TSV : 0) | (normal_given ? MP_STREAM_NORMAL_FASTA : 0);
+        mp_filtered* f = nullptr;
+        if (mp_batch_create(ctx, ds, mode, window_len, 0, mp_dataset_num_genes(ds), &batch) != 0 || mp_batch_run(ctx, batch, nullptr) != 0 ||
+            mp_batch_filter_binary(ctx, batch, filt_ref_bytes.data(), filt_ref_bytes.size(), uint32_t(peptide_len), streams, &res, &f) != 0) {
+            int rc = fail(ctx, "microphaser");
+            mp_batch_free(batch); mp_dataset_free(ds); mp_destroy(ctx);
+            return rc;
+        }
+        int rc = 0;
+        size_t n = 0;
+        const char* p = mp_filtered_fasta(f, &n);   // what `filter` writes, in its order
+        if (!write_stdout(p, n)) { std::fprintf(stderr, "cannot write the filtered FASTA to stdout\n"); rc = 1; }
+        p = mp_filtered_normal_fasta(f, &n);
+        if (!rc && !write_file(f_norm, p, n)) { std::fprintf(stderr, "cannot write %s\n", f_norm.c_str()); rc = 1; }
+        p = mp_filtered_tsv(f, &n);
+        if (!rc && !write_file(f_tsv, p, n)) { std::fprintf(stderr, "cannot write %s\n", f_tsv.c_str()); rc = 1; }
+        p = mp_filtered_removed_tsv(f, &n);
+        if (!rc && !write_file(f_sim, p, n)) { std::fprintf(stderr, "cannot write %s\n", f_sim.c_str()); rc = 1; }
+        p = mp_filtered_removed_fasta(f, &n);
+        if (!rc && !write_file(f_rem, p, n)) { std::fprintf(stderr, "cannot write %s\n", f_rem.c_str()); rc = 1; }
+        if (res) {   // the somatic streams asked for
+            p = mp_results_tsv(res, &n);
+            if (!rc && tsv_given && !write_file(tsv, p, n)) { std::fprintf(stderr, "cannot write %s\n", tsv.c_str()); rc = 1; }
+            p = mp_results_normal_fasta(res, &n);
+            if (!rc && normal_given && !write_file(normal, p, n)) { std::fprintf(stderr, "cannot write %s\n", normal.c_str()); rc = 1; }
+            mp_results_free(res);
+        }
+        mp_filtered_free(f);
+        mp_batch_free(batch);
+        mp_dataset_free(ds);
+        mp_destroy(ctx);
+        return rc;
+    }
     if (pep_mode) {
         mp_peptides* pep = nullptr;
         if (mp_batch_create(ctx, ds, mode, window_len, 0, mp_dataset_num_genes(ds), &batch) != 0 || mp_batch_run(ctx, batch, nullptr) != 0 ||

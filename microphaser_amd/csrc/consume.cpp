@@ -132,6 +132,58 @@ void record_add_freq(IDRecord& r, double freq) {
 // MP_TRACE=<file>: one line per print_haplotypes call / merge (debugging aid: the oracle writes the same trace)
 static const char* trace_path() { static const char* const p = std::getenv("MP_TRACE"); return p; }
 
+// The `somatic` consumer's output for one gene range: the text streams and, for a fused filter (mp_batch_filter), one Row per row the
+// TSV stream holds - or would hold, whether or not its text is written - with the places of its two windows.
+struct SomaticPart : SomaticText {
+    bool want_rows = false;
+    RowVec rows;
+    PodVec<RowSeq> seq;           // 2 per row
+    TextArena text;               // the rows' text that does not live in the gene model or the downloaded records
+    uint64_t side_bytes = 0;      // the merged rows' sequences (held in `text`): this range's share of RowCapture::side
+    Row& add_row(std::string_view id, std::string_view transcript, std::string_view gene_id, std::string_view gene_name, std::string_view chrom,
+                 uint64_t offset, uint64_t frame, double freq, uint32_t depth, uint32_t nvar, uint32_t nsomatic, uint32_t nvariant_sites,
+                 uint32_t nsomvariant_sites, std::string_view strand, std::string_view variant_sites, std::string_view somatic_positions,
+                 std::string_view somatic_aa_change, std::string_view germline_positions, std::string_view germline_aa_change) {
+        rows.emplace_back();
+        Row& r = rows.back();
+        r.id = text.put(id); r.transcript = transcript; r.gene_id = gene_id; r.gene_name = gene_name; r.chrom = chrom;
+        r.offset = offset; r.frame = frame;
+        r.freq = freq == freq ? freq : std::numeric_limits<double>::quiet_NaN();   // (what strtod reads back from the "NaN" cur_f64 writes)
+        r.depth = depth; r.nvar = nvar; r.nsomatic = nsomatic; r.nvariant_sites = nvariant_sites; r.nsomvariant_sites = nsomvariant_sites;
+        r.strand = strand; r.variant_sites = text.put(variant_sites); r.somatic_positions = text.put(somatic_positions);
+        r.somatic_aa_change = text.put(somatic_aa_change); r.germline_positions = text.put(germline_positions);
+        r.germline_aa_change = text.put(germline_aa_change);
+        return r;
+    }
+    static uint8_t rev_of(const Row& r) { return (!r.id.empty() && r.id.back() == 'F') ? 0 : SRC_REV; }   // (filter, src/peptides.rs:291-294)
+    // a row printed by print_haplotypes: its windows are slices [off, off + len) of the device record `slot` (views into its host copy)
+    void add_windows(Row& r, uint64_t slot, const uint8_t* rseq, std::string_view mutant, const uint8_t* rgerm, std::string_view normal) {
+        const uint8_t rv = rev_of(r);
+        auto one = [&](const uint8_t* base, std::string_view v, uint8_t half) {
+            if (v.empty()) return RowSeq{0, 0, 0, rv, 0};
+            const uint64_t off = uint64_t(reinterpret_cast<const uint8_t*>(v.data()) - base);
+            if (off > 0xFFFF || v.size() > 0xFFFF) throw Error("internal error: row window outside the record");
+            return RowSeq{slot, uint32_t(v.size()), uint16_t(off), uint8_t(half | rv), 0};
+        };
+        r.mutant_sequence = mutant;
+        r.normal_sequence = normal;
+        seq.push_back(one(rseq, mutant, 0));
+        seq.push_back(one(rgerm, normal, SRC_GERM));
+    }
+    // a row of the splice-side merge: its windows were built on the host and go to the side buffer (offsets re-based in gather_rows)
+    void add_merged_windows(Row& r, std::string_view mutant, std::string_view normal) {
+        const uint8_t rv = rev_of(r);
+        auto one = [&](std::string_view v, SV& field) {
+            field = text.put(v);
+            if (v.empty()) { seq.push_back(RowSeq{0, 0, 0, rv, 0}); return; }
+            seq.push_back(RowSeq{side_bytes, uint32_t(v.size()), 0, uint8_t(SRC_MERGE | rv), 0});
+            side_bytes += v.size();
+        };
+        one(mutant, r.mutant_sequence);
+        one(normal, r.normal_sequence);
+    }
+};
+
 struct ConsumerHooks {
     static constexpr bool kNormal = false;
     const Batch& b;
@@ -140,7 +192,7 @@ struct ConsumerHooks {
     const Gene& gene;
     const Transcript& transcript;
     const TxDev& T;
-    SomaticText& out;
+    SomaticPart& out;
     uint64_t window_len;
     size_t next_step = 0, cur_step = 0;
     bool is_fwd;
@@ -392,6 +444,10 @@ struct ConsumerHooks {
                     // the row is written field by field (no copy through the record)
                     put_tsv_row(out, idstr, transcript.id, gene.id, gene.name, gene.chrom, roffset, frame, frame_frequency, wd.nrows, n_variants,
                                 n_somatic, n_sites, n_som_sites, strand_s, sites, som_pos, som_pc, germ_pos, germ_pc, normal_peptide, neopeptide);
+                    if (out.want_rows)   // (whether or not the TSV text is written)
+                        out.add_windows(out.add_row(idstr, transcript.id, gene.id, gene.name, gene.chrom, roffset, frame, frame_frequency, wd.nrows,
+                                                    n_variants, n_somatic, n_sites, n_som_sites, strand_s, sites, som_pos, som_pc, germ_pos, germ_pc),
+                                        gs.rec, rseq, neopeptide, rgerm, normal_peptide);
                 }
                 // The record is kept for every window that is marked as feeding a merge; an emitted window keeps it too where a merge can
                 // reach a window the planner's marks miss: window lengths that are not a multiple of 3, or an indel / frameshift context
@@ -570,6 +626,14 @@ struct ConsumerHooks {
                         if (out.streams & STREAM_NORMAL_FASTA) put_fasta(out.normal_fasta, out_record.id, reinterpret_cast<const uint8_t*>(out_wt.data()), size_t(window_len));
                     }
                     put_tsv_row(out, out_record);
+                    if (out.want_rows) {
+                        const IDRecord& o = out_record;
+                        out.add_merged_windows(out.add_row(o.id, out.text.put(o.transcript), out.text.put(o.gene_id), out.text.put(o.gene_name),
+                                                           out.text.put(o.chrom), o.offset, o.frame, o.freq, o.depth, o.nvar, o.nsomatic, o.nvariant_sites,
+                                                           o.nsomvariant_sites, out.text.put(o.strand), o.variant_sites, o.somatic_positions,
+                                                           o.somatic_aa_change, o.germline_positions, o.germline_aa_change),
+                                               o.mutant_sequence, o.normal_sequence);
+                    }
                 }
             }
             if (eg.is_short) prev_hap_vec = std::move(new_hap_vec);
@@ -997,9 +1061,48 @@ void assemble(std::vector<Out>& parts, PhasedStreams& out, size_t nthreads) {
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_release).count());
 }
 
-inline void want_sources(SomaticText&, bool) {}
+inline void want_sources(SomaticPart&, bool) {}
 inline void want_sources(NormalPart& p, bool on) { p.want_sources = on; }
-inline void gather_sources(std::vector<SomaticText>&, PepSources*, uint64_t, size_t) {}
+inline void want_rows(SomaticPart& p, bool on) { p.want_rows = on; }
+inline void want_rows(NormalPart&, bool) {}
+inline void gather_sources(std::vector<SomaticPart>&, PepSources*, uint64_t, size_t) {}
+inline void gather_rows(std::vector<NormalPart>&, RowCapture*, size_t) {}
+// the parts' rows, concatenated in gene order (merged windows copied into the joined side buffer, their offsets re-based), on all host
+// threads; the text arenas move into the capture
+void gather_rows(std::vector<SomaticPart>& parts, RowCapture* C, size_t nthreads) {
+    if (!C) return;
+    const size_t np = parts.size();
+    std::vector<size_t> r_at(np + 1, 0), b_at(np + 1, 0);
+    for (size_t t = 0; t < np; t++) { r_at[t + 1] = r_at[t] + parts[t].rows.size(); b_at[t + 1] = b_at[t] + parts[t].side_bytes; }
+    C->rows.resize(r_at[np]);
+    advise_huge(C->rows.data(), C->rows.size() * sizeof(Row));
+    C->seq.resize(2 * r_at[np]);
+    C->side.resize(b_at[np]);
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t t; (t = next.fetch_add(1)) < np;) {
+            SomaticPart& P = parts[t];
+            if (!P.rows.empty()) std::memcpy(C->rows.data() + r_at[t], P.rows.data(), P.rows.size() * sizeof(Row));
+            RowSeq* d = C->seq.data() + 2 * r_at[t];
+            for (size_t i = 0; i < P.seq.size(); i++) {
+                d[i] = P.seq[i];
+                if (d[i].flags & SRC_MERGE) {
+                    const Row& r = P.rows[i / 2];
+                    const SV& v = (i & 1) ? r.normal_sequence : r.mutant_sequence;
+                    d[i].at += b_at[t];
+                    std::memcpy(C->side.data() + d[i].at, v.data(), v.size());
+                }
+            }
+            RowVec().swap(P.rows);
+            PodVec<RowSeq>().swap(P.seq);
+        }
+    };
+    std::vector<std::thread> th;
+    for (size_t k = 1; k < std::max<size_t>(1, std::min(nthreads, np)); k++) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+    for (SomaticPart& P : parts) C->text.push_back(std::move(P.text));
+}
 // the parts' sources, concatenated in gene order (merge indices re-based onto the joined merge buffer), on all host threads
 void gather_sources(std::vector<NormalPart>& parts, PepSources* S, uint64_t window_len, size_t nthreads) {
     if (!S) return;
@@ -1033,7 +1136,7 @@ void gather_sources(std::vector<NormalPart>& parts, PepSources* S, uint64_t wind
 }
 
 template <class Hooks, class Out>
-void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams, PepSources* sources) {
+void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams, PepSources* sources, RowCapture* rows) {
     size_t nthreads = host_threads();
     const size_t ng = b.genes.size();
     if (nthreads > ng) nthreads = ng ? ng : 1;
@@ -1041,8 +1144,10 @@ void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out,
         std::vector<Out> one(1);
         one[0].streams = streams;
         want_sources(one[0], sources != nullptr);
+        want_rows(one[0], rows != nullptr);
         consume_range<Hooks>(b, res, 0, ng, one[0]);
         gather_sources(one, sources, b.window_len, 1);
+        gather_rows(one, rows, 1);
         assemble(one, out, 1);
         return;
     }
@@ -1063,7 +1168,7 @@ void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out,
     }
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<Out> parts(nthreads);
-    for (Out& p : parts) { p.streams = streams; want_sources(p, sources != nullptr); }
+    for (Out& p : parts) { p.streams = streams; want_sources(p, sources != nullptr); want_rows(p, rows != nullptr); }
     std::vector<std::string> errors(nthreads);
     std::vector<std::thread> th;
     // Reserve each range's streams up front (an estimate from the records the device produced, shared out by planned steps; pages
@@ -1083,6 +1188,7 @@ void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out,
     for (size_t t = 0; t < nthreads; t++)
         if (!errors[t].empty()) throw Error(errors[t]);  // the first failing gene range in gene order, like a sequential run
     gather_sources(parts, sources, b.window_len, nthreads);
+    gather_rows(parts, rows, nthreads);
     const auto t1 = std::chrono::steady_clock::now();
     assemble(parts, out, nthreads);
     if (std::getenv("MP_DEBUG"))
@@ -1092,14 +1198,14 @@ void consume_sharded(const Batch& b, const HostResults& res, PhasedStreams& out,
 
 }  // namespace
 
-void consume_batch(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams) {
+void consume_batch(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams, RowCapture* rows) {
     if (b.normal) throw Error("internal error: somatic consumer on a normal-mode batch");
-    consume_sharded<ConsumerHooks, SomaticText>(b, res, out, streams, nullptr);
+    consume_sharded<ConsumerHooks, SomaticPart>(b, res, out, streams, nullptr, rows);
 }
 
 void consume_batch_normal(const Batch& b, const HostResults& res, PhasedStreams& out, uint32_t streams, PepSources* sources) {
     if (!b.normal) throw Error("internal error: normal consumer on a somatic-mode batch");
-    consume_sharded<NormalConsumerHooks, NormalPart>(b, res, out, streams, sources);
+    consume_sharded<NormalConsumerHooks, NormalPart>(b, res, out, streams, sources, nullptr);
 }
 
 }  // namespace mp

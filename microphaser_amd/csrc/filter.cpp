@@ -32,33 +32,6 @@ namespace mp {
 
 namespace {
 
-// One row of info.tsv (IDRecord, src/common.rs:350-373): text fields as views into the TSV buffer (or, for a quoted field, into the
-// arena that holds its unescaped form), numbers parsed.
-// a string_view without a constructor, so that a Row can be created uninitialised (the parsing threads fill 8.8 M of them in place)
-struct SV {
-    const char* p;
-    size_t n;
-    SV& operator=(std::string_view v) { p = v.data(); n = v.size(); return *this; }
-    operator std::string_view() const { return std::string_view(p, n); }
-    bool empty() const { return n == 0; }
-    size_t size() const { return n; }
-    const char* data() const { return p; }
-    char back() const { return p[n - 1]; }
-    size_t find(char c) const { return std::string_view(p, n).find(c); }
-};
-inline bool operator==(const SV& a, const SV& b) { return std::string_view(a) == std::string_view(b); }
-inline bool operator!=(const SV& a, const SV& b) { return !(a == b); }
-inline bool operator==(const SV& a, const char* b) { return std::string_view(a) == std::string_view(b); }
-
-struct Row {
-    SV id, transcript, gene_id, gene_name, chrom, strand, variant_sites, somatic_positions, somatic_aa_change, germline_positions,
-        germline_aa_change, normal_sequence, mutant_sequence;
-    uint64_t offset, frame;
-    double freq;
-    uint32_t depth, nvar, nsomatic, nvariant_sites, nsomvariant_sites;
-};
-using RowVec = PodVec<Row>;   // rows are sized once and filled in place by the parsing threads (no zero fill: 250 bytes x 8.8 M rows)
-
 uint64_t field_u64(std::string_view s, const char* name) {
     uint64_t v = 0;
     const auto r = std::from_chars(s.data(), s.data() + s.size(), v);
@@ -292,10 +265,22 @@ typename V::value_type* to_device(const V& v, hipStream_t stream, std::vector<vo
     return static_cast<T*>(p);
 }
 
-}  // namespace
+// Wall times of the phases on stderr (MP_DEBUG)
+struct Laps {
+    bool dbg = std::getenv("MP_DEBUG") != nullptr;
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        const auto now = std::chrono::steady_clock::now();
+        if (dbg) std::fprintf(stderr, "[mp]   filter: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        t_prev = now;
+    }
+};
 
-void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
-                   uint32_t L, FilterResult& out) {
+// What both row sources do first: the device, and the reference peptidome - bincode v1 HashSet<Vec<u8>> (deserialize_from(...).unwrap(),
+// :242) -> keys of the length-L members; or the sorted distinct keys themselves (a peptidome that never left the library, reference_keys
+// != nullptr: ref_keys stays empty). Keys of key_words(L) words each (pep.hpp).
+void filter_begin(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, uint32_t L, FilterResult& out,
+                  std::vector<uint64_t>& ref_keys, Laps& lap) {
     check_peptide_len(L);
     const uint32_t w = key_words(L);
     out = FilterResult();
@@ -303,18 +288,6 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         throw Error("no HIP device available: `filter` translates and scores on the GPU, there is no CPU fallback");
     HIP_OK(hipSetDevice(device));
-    const bool dbg = std::getenv("MP_DEBUG") != nullptr;   // wall time of the phases on stderr
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        const auto now = std::chrono::steady_clock::now();
-        if (dbg) std::fprintf(stderr, "[mp]   filter: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
-    const size_t threads = host_threads();
-
-    // ---- reference peptidome: bincode v1 HashSet<Vec<u8>> (deserialize_from(...).unwrap(), :242) -> keys of the length-L members;
-    //      or the sorted distinct keys themselves (a peptidome that never left the library). Keys of w words each (pep.hpp).
-    std::vector<uint64_t> ref_keys;
     if (!reference_keys) {
         size_t p = 0;
         auto u64 = [&]() {
@@ -339,46 +312,18 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
         }
     }
     lap("reference set decoded");
+}
 
-    // ---- rows and their two nucleotide windows
-    RowVec rows;
-    std::deque<std::string> arena;
-    parse_tsv(tsv_text, rows, arena);
-    lap("tsv parsed");
+// The common part of both row sources: the reference keys sorted on the device, K5, then the row stream, K6 and the emission. The
+// source supplies the rows (in TSV order) and K5 in two steps: offsets(stream, owned) fills aa_off (n_seq + 1 entries: sequence s =
+// 2r mutant, 2r + 1 normal of row r) and returns it on the device; launch(stream, d_aa_off, d_ref, n_ref, d_aa, d_flags, d_err) enqueues
+// the translation.
+template <class Offsets, class Launch>
+void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64_t>& ref_keys, uint32_t L, const RowVec& rows,
+                 PodVec<uint64_t>& aa_off, Offsets offsets, Launch launch, Laps& lap, FilterResult& out) {
+    const uint32_t w = key_words(L);
+    const size_t threads = host_threads();
     out.n_rows = rows.size();
-    const size_t n_seq = rows.size() * 2;   // 2r = mutant, 2r + 1 = normal
-    PodVec<uint8_t> nt, rev(n_seq);
-    PodVec<uint64_t> nt_off(n_seq), aa_off(n_seq + 1);
-    PodVec<uint32_t> nt_len(n_seq);
-    aa_off[0] = 0;
-    {
-        uint64_t at = 0;
-        for (size_t r = 0; r < rows.size(); r++) {
-            const uint8_t rv = (!rows[r].id.empty() && rows[r].id.back() == 'F') ? 0 : 1;  // :291-294
-            const std::string_view seqs[2] = {rows[r].mutant_sequence, rows[r].normal_sequence};
-            for (int k = 0; k < 2; k++) {
-                const size_t s = 2 * r + k;
-                if (seqs[k].size() > 0xFFFFFFFFull) throw Error("sequence too long");
-                nt_off[s] = at;
-                nt_len[s] = uint32_t(seqs[k].size());
-                rev[s] = rv;
-                at += seqs[k].size();
-                aa_off[s + 1] = aa_off[s] + (seqs[k].size() > 2 ? (seqs[k].size() - 2 + 2) / 3 : 0);
-            }
-        }
-        nt.resize(at);
-        advise_huge(nt.data(), nt.size());
-        const size_t parts = std::min<size_t>(threads, rows.size() / 65536 + 1);
-        run_parts(parts, [&](size_t t) {
-            for (size_t r = rows.size() * t / parts, e = rows.size() * (t + 1) / parts; r < e; r++) {
-                if (nt_len[2 * r]) std::memcpy(nt.data() + nt_off[2 * r], rows[r].mutant_sequence.data(), nt_len[2 * r]);
-                if (nt_len[2 * r + 1]) std::memcpy(nt.data() + nt_off[2 * r + 1], rows[r].normal_sequence.data(), nt_len[2 * r + 1]);
-            }
-        });
-    }
-    const uint64_t n_aa = aa_off[n_seq];
-    lap("windows laid out");
-
     hipStream_t stream;
     HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     hipEvent_t e0, e1, e2, e3;
@@ -406,11 +351,8 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
             d_ref = static_cast<uint64_t*>(d_out);
         }
         // ---- K5
-        uint8_t* d_nt = to_device(nt, stream, owned, 64);
-        uint64_t* d_nt_off = to_device(nt_off, stream, owned);
-        uint32_t* d_nt_len = to_device(nt_len, stream, owned);
-        uint8_t* d_rev = to_device(rev, stream, owned);
-        uint64_t* d_aa_off = to_device(aa_off, stream, owned);
+        const uint64_t* d_aa_off = offsets(stream, owned);
+        const uint64_t n_aa = aa_off[rows.size() * 2];
         void *d_aa = nullptr, *d_flags = nullptr, *d_err = nullptr;
         HIP_OK(hipMalloc(&d_aa, n_aa + 16)); owned.push_back(d_aa);
         HIP_OK(hipMalloc(&d_flags, n_aa + 16)); owned.push_back(d_flags);
@@ -418,8 +360,7 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
         HIP_OK(hipMemsetAsync(d_err, 0, 4, stream));
         HIP_OK(hipMemsetAsync(d_flags, 0, n_aa + 16, stream));
         HIP_OK(hipEventRecord(e0, stream));
-        device_translate_records(d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq, L, d_ref, n_ref, static_cast<uint8_t*>(d_aa),
-                                 static_cast<uint8_t*>(d_flags), static_cast<uint32_t*>(d_err), stream);
+        launch(stream, d_aa_off, d_ref, n_ref, static_cast<uint8_t*>(d_aa), static_cast<uint8_t*>(d_flags), static_cast<uint32_t*>(d_err));
         HIP_OK(hipEventRecord(e1, stream));
         PodVec<uint8_t> aa(n_aa), flags(n_aa);
         uint32_t err = 0;
@@ -667,6 +608,104 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
         throw;
     }
     cleanup();
+}
+
+}  // namespace
+
+void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
+                   uint32_t L, FilterResult& out) {
+    Laps lap;
+    std::vector<uint64_t> ref_keys;
+    filter_begin(device, reference_binary, reference_keys, L, out, ref_keys, lap);
+    // ---- rows and their two nucleotide windows, laid out back to back for the upload
+    RowVec rows;
+    std::deque<std::string> arena;
+    parse_tsv(tsv_text, rows, arena);
+    lap("tsv parsed");
+    const size_t n_seq = rows.size() * 2;   // 2r = mutant, 2r + 1 = normal
+    PodVec<uint8_t> nt, rev(n_seq);
+    PodVec<uint64_t> nt_off(n_seq), aa_off(n_seq + 1);
+    PodVec<uint32_t> nt_len(n_seq);
+    aa_off[0] = 0;
+    {
+        uint64_t at = 0;
+        for (size_t r = 0; r < rows.size(); r++) {
+            const uint8_t rv = (!rows[r].id.empty() && rows[r].id.back() == 'F') ? 0 : 1;  // :291-294
+            const std::string_view seqs[2] = {rows[r].mutant_sequence, rows[r].normal_sequence};
+            for (int k = 0; k < 2; k++) {
+                const size_t s = 2 * r + k;
+                if (seqs[k].size() > 0xFFFFFFFFull) throw Error("sequence too long");
+                nt_off[s] = at;
+                nt_len[s] = uint32_t(seqs[k].size());
+                rev[s] = rv;
+                at += seqs[k].size();
+                aa_off[s + 1] = aa_off[s] + (seqs[k].size() > 2 ? (seqs[k].size() - 2 + 2) / 3 : 0);
+            }
+        }
+        nt.resize(at);
+        advise_huge(nt.data(), nt.size());
+        const size_t parts = std::min<size_t>(host_threads(), rows.size() / 65536 + 1);
+        run_parts(parts, [&](size_t t) {
+            for (size_t r = rows.size() * t / parts, e = rows.size() * (t + 1) / parts; r < e; r++) {
+                if (nt_len[2 * r]) std::memcpy(nt.data() + nt_off[2 * r], rows[r].mutant_sequence.data(), nt_len[2 * r]);
+                if (nt_len[2 * r + 1]) std::memcpy(nt.data() + nt_off[2 * r + 1], rows[r].normal_sequence.data(), nt_len[2 * r + 1]);
+            }
+        });
+    }
+    lap("windows laid out");
+    const uint8_t* d_nt = nullptr;
+    const uint64_t* d_nt_off = nullptr;
+    const uint32_t* d_nt_len = nullptr;
+    const uint8_t* d_rev = nullptr;
+    filter_rows(reference_keys, ref_keys, L, rows, aa_off,
+        [&](hipStream_t stream, std::vector<void*>& owned) -> const uint64_t* {
+            d_nt = to_device(nt, stream, owned, 64);
+            d_nt_off = to_device(nt_off, stream, owned);
+            d_nt_len = to_device(nt_len, stream, owned);
+            d_rev = to_device(rev, stream, owned);
+            return to_device(aa_off, stream, owned);
+        },
+        [&](hipStream_t stream, const uint64_t* d_aa_off, const uint64_t* d_ref, uint64_t n_ref, uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err) {
+            device_translate_records(d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq, L, d_ref, n_ref, d_aa, d_flags, d_err, stream);
+        },
+        lap, out);
+}
+
+void filter_captured(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, const RowCapture& cap,
+                     const RecArena& arena, uint32_t L, FilterResult& out) {
+    Laps lap;
+    std::vector<uint64_t> ref_keys;
+    filter_begin(device, reference_binary, reference_keys, L, out, ref_keys, lap);
+    // every sequence must lie inside what it names: K5 reads [off, off + len) of a record's half, or [at, at + len) of the side buffer
+    const size_t n_seq = cap.rows.size() * 2;
+    if (cap.seq.size() != n_seq) throw Error("internal error: captured rows and sequences disagree");
+    for (const RowSeq& rs : cap.seq) {
+        const bool ok = (rs.flags & SRC_MERGE) ? (rs.at <= cap.side.size() && rs.len <= cap.side.size() - rs.at)
+                                               : (rs.len == 0 || (rs.at < arena.n_slots && uint64_t(rs.off) + rs.len <= arena.seq_cap));
+        if (!ok) throw Error("internal error: captured sequence outside the record arena");
+    }
+    if (n_seq && !arena.recs) throw Error("internal error: no device record arena");
+    PodVec<uint64_t> aa_off(n_seq + 1);
+    aa_off[0] = 0;
+    lap("captured rows checked");
+    const RowSeq* d_seq = nullptr;
+    const uint8_t* d_side = nullptr;
+    filter_rows(reference_keys, ref_keys, L, cap.rows, aa_off,
+        [&](hipStream_t stream, std::vector<void*>& owned) -> const uint64_t* {
+            d_seq = to_device(cap.seq, stream, owned);
+            d_side = to_device(cap.side, stream, owned);
+            uint64_t* d_aa_off = nullptr;
+            HIP_OK(hipMalloc(&d_aa_off, (n_seq + 1) * 8)); owned.push_back(d_aa_off);
+            device_row_codon_offsets(d_seq, n_seq, d_aa_off, stream);
+            HIP_OK(hipMemcpyAsync(aa_off.data(), d_aa_off, (n_seq + 1) * 8, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            return d_aa_off;
+        },
+        [&](hipStream_t stream, const uint64_t* d_aa_off, const uint64_t* d_ref, uint64_t n_ref, uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err) {
+            device_translate_row_sources(d_seq, n_seq, arena.recs, arena.rec_stride, arena.seq_cap, d_side, d_aa_off, L, d_ref, n_ref, d_aa, d_flags,
+                                         d_err, stream);
+        },
+        lap, out);
 }
 
 }  // namespace mp

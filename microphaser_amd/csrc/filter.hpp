@@ -3,13 +3,85 @@
 // Translation + peptidome membership (K5) and the per-group statistics (K6) run on the device; the row-stream
 // bookkeeping of the reference (stop-gain suppression, per-variant-region grouping, de-duplication) stays on the host.
 #pragma once
+#include <algorithm>
+#include <cstring>
+#include <memory>
 #include <string>
 #include <string_view>
 #include <vector>
 
 #include "model.hpp"
+#include "pep.hpp"
 
 namespace mp {
+
+// One row of info.tsv (IDRecord, src/common.rs:350-373): text fields as views (into the TSV text, the unescaped form of a quoted
+// field, or - for rows captured by the `somatic` consumer - the gene model, a capture's TextArena or the downloaded record arena),
+// numbers as values.
+// a string_view without a constructor, so that a Row can be created uninitialised (the parsing threads fill 8.8 M of them in place)
+struct SV {
+    const char* p;
+    size_t n;
+    SV& operator=(std::string_view v) { p = v.data(); n = v.size(); return *this; }
+    operator std::string_view() const { return std::string_view(p, n); }
+    bool empty() const { return n == 0; }
+    size_t size() const { return n; }
+    const char* data() const { return p; }
+    char back() const { return p[n - 1]; }
+    size_t find(char c) const { return std::string_view(p, n).find(c); }
+};
+inline bool operator==(const SV& a, const SV& b) { return std::string_view(a) == std::string_view(b); }
+inline bool operator!=(const SV& a, const SV& b) { return !(a == b); }
+inline bool operator==(const SV& a, const char* b) { return std::string_view(a) == std::string_view(b); }
+
+struct Row {
+    SV id, transcript, gene_id, gene_name, chrom, strand, variant_sites, somatic_positions, somatic_aa_change, germline_positions,
+        germline_aa_change, normal_sequence, mutant_sequence;
+    uint64_t offset, frame;
+    double freq;
+    uint32_t depth, nvar, nsomatic, nvariant_sites, nsomvariant_sites;
+};
+using RowVec = PodVec<Row>;   // rows are sized once and filled in place (no zero fill: 250 bytes x 8.8 M rows)
+
+// ---- `somatic` -> `filter` without the TSV text: the rows the `somatic` consumer would write, captured as Rows (consume.cpp), and
+// for each the place of its two nucleotide windows, which K5 reads where they lie (kernels_filter.hip k5_translate_row_sources).
+enum : uint8_t { SRC_GERM = 4 };   // (beside pep.hpp's SRC_REV, SRC_MERGE)
+struct RowSeq {          // 16 bytes; row r's mutant window is seq[2r], its normal window seq[2r + 1]
+    uint64_t at;         // SRC_MERGE clear: record slot in the device arena (GroupSum::rec); set: byte offset in RowCapture::side
+    uint32_t len;        // bases (0: no normal window)
+    uint16_t off;        // first base within the record's half (device records only)
+    uint8_t flags;       // SRC_GERM: the record's germline half (rec_germ); SRC_REV: reverse-complement (the row id does not end in 'F')
+    uint8_t pad;
+};
+static_assert(sizeof(RowSeq) == 16, "RowSeq layout");
+
+// Stable storage for the text fields of captured rows (the consumer's list fields live in per-thread scratch): blocks that never move.
+struct TextArena {
+    std::vector<std::unique_ptr<char[]>> blocks;
+    char* at = nullptr;
+    size_t left = 0;
+    std::string_view put(std::string_view s) {
+        if (s.empty()) return std::string_view();
+        if (s.size() > left) {
+            const size_t n = std::max<size_t>(s.size(), size_t(1) << 20);
+            blocks.emplace_back(new char[n]);
+            at = blocks.back().get();
+            left = n;
+        }
+        std::memcpy(at, s.data(), s.size());
+        const std::string_view v(at, s.size());
+        at += s.size();
+        left -= s.size();
+        return v;
+    }
+};
+
+struct RowCapture {      // the rows of a `somatic` batch in TSV order
+    RowVec rows;
+    PodVec<RowSeq> seq;                          // 2 per row
+    PodVec<uint8_t> side;                        // the sequences of the splice-side merges' rows, back to back
+    std::vector<TextArena> text;                 // owns the copied text fields
+};
 
 struct FilterResult {
     PodVec<char> fasta;          // stdout: kept tumor peptides
@@ -26,5 +98,11 @@ struct FilterResult {
 // tsv_text: info.tsv of `somatic`. Both buffers are read in place and must stay valid for the call.
 void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
                    uint32_t peptide_len, FilterResult& out);
+
+// The same on rows captured from a `somatic` batch that is still resident on `device`: the windows are read from its record arena and
+// from cap.side (k5_translate_row_sources) - no TSV text, no parse, no upload of the windows. Same bytes, counts and errors as
+// filter_device on the TSV those rows would have been written as. The views of cap.rows must stay valid for the call.
+void filter_captured(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, const RowCapture& cap,
+                     const RecArena& arena, uint32_t peptide_len, FilterResult& out);
 
 }  // namespace mp

@@ -1,13 +1,21 @@
 // K5 / K6: the device side of `microphaser filter` (reference: src/peptides.rs:188-709).
 //   K5 translates the mutant / normal nucleotide windows of the neopeptide table and tests every peptide of the tumor
 //      protein against the reference peptidome (sorted 5-bit keys, binary search; u64 keys for L <= 12, 16-byte keys for
-//      13 <= L <= 25, pep.hpp) - byte / integer work.
+//      13 <= L <= 25, pep.hpp) - byte / integer work. Two forms share the per-sequence body: k5_translate_records reads the windows
+//      of a parsed TSV from one uploaded buffer, k5_translate_row_sources reads those of captured rows where they lie (the record
+//      arena of the resident `somatic` batch, or a small buffer of splice-side merges).
 //   K6 evaluates, per group of records that share a variant region, the binomial likelihood grid, its Simpson integral
 //      in log space and the iterative 95 % credible-interval search - f64, transcendental-bound, one thread per group.
 //      Restates statrs 0.15 Binomial::pmf / ln_binomial / ln_gamma and bio 0.34 LogProb::{ln_simpsons_integrate_exp,
 //      ln_sum_exp}; ln(k!) for k <= 170 comes from a host-built table (ln of the cached f64 factorials, as statrs does).
 #include <hip/hip_runtime.h>
 
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/functional.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include "filter.hpp"
 #include "kernels_filter.hpp"
 #include "pep.hpp"
 
@@ -25,21 +33,14 @@ __device__ __forceinline__ int base2f(uint8_t c, bool complement) {
     return complement ? 3 - b : b;
 }
 
-// K = uint64_t (L <= 12) or unsigned __int128 (13 <= L <= 25): the rolling key lives in registers, one K-sized load per probe
+// to_protein of the len bases at q (reverse complement first when rc) into out[0 .. codons), then for every peptide_len-mer of it the
+// flags: bit0 = an 'X' within the peptide, bit1 = the key is in ref_keys. K = uint64_t (L <= 12) or unsigned __int128 (13 <= L <= 25):
+// the rolling key lives in registers, one K-sized load per probe. Both K5 forms resolve their sequence to a byte pointer and call this.
 template <class K>
-__global__ __launch_bounds__(256) void k5_translate_records(const uint8_t* __restrict__ nt, const uint64_t* __restrict__ nt_off,
-                                                            const uint32_t* __restrict__ nt_len, const uint8_t* __restrict__ rev,
-                                                            const uint64_t* __restrict__ aa_off, uint64_t n_seq, uint32_t L,
-                                                            const K* __restrict__ ref_keys, uint64_t n_ref, uint8_t* __restrict__ aa,
-                                                            uint8_t* __restrict__ flags, uint32_t* __restrict__ err) {
-    const uint64_t s = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (s >= n_seq) return;
-    const uint32_t len = nt_len[s];
+__device__ __forceinline__ void k5_sequence(const uint8_t* __restrict__ q, uint32_t len, bool rc, uint32_t L, const K* __restrict__ ref_keys,
+                                            uint64_t n_ref, uint8_t* __restrict__ out, uint8_t* __restrict__ fl, uint32_t* __restrict__ err) {
     if (len == 0) return;                      // empty normal_sequence: no protein (:296-299)
     if (len < 2) { atomicOr(err, 2u); return; }  // `r.len() - 2` underflows (:139)
-    const uint8_t* q = nt + nt_off[s];
-    const bool rc = rev[s] != 0;
-    uint8_t* out = aa + aa_off[s];
     const uint32_t ncod = len > 2 ? (len - 2 + 2) / 3 : 0;   // i = 0, 3, ... while i < len - 2
     K kmask;
     if constexpr (sizeof(K) == 8) kmask = L >= 12 ? ~0ull >> 4 : ((1ull << (5 * L)) - 1ull);
@@ -65,10 +66,36 @@ __global__ __launch_bounds__(256) void k5_translate_records(const uint8_t* __res
                 if (r < key) lo = mid + 1; else hi = mid;
             }
             if (lo < n_ref && ref_keys[lo] == key) f |= 2;
-            flags[aa_off[s] + (j + 1 - L)] = f;
+            fl[j + 1 - L] = f;
         }
     }
     if (bad) atomicOr(err, 1u);
+}
+
+template <class K>
+__global__ __launch_bounds__(256) void k5_translate_records(const uint8_t* __restrict__ nt, const uint64_t* __restrict__ nt_off,
+                                                            const uint32_t* __restrict__ nt_len, const uint8_t* __restrict__ rev,
+                                                            const uint64_t* __restrict__ aa_off, uint64_t n_seq, uint32_t L,
+                                                            const K* __restrict__ ref_keys, uint64_t n_ref, uint8_t* __restrict__ aa,
+                                                            uint8_t* __restrict__ flags, uint32_t* __restrict__ err) {
+    const uint64_t s = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (s >= n_seq) return;
+    k5_sequence<K>(nt + nt_off[s], nt_len[s], rev[s] != 0, L, ref_keys, n_ref, aa + aa_off[s], flags + aa_off[s], err);
+}
+
+// One thread per captured sequence (at most 240 nt): the bases come from the record arena of the resident batch or the side buffer.
+template <class K>
+__global__ __launch_bounds__(256) void k5_translate_row_sources(const RowSeq* __restrict__ seq, uint64_t n_seq, const uint8_t* __restrict__ recs,
+                                                                uint32_t rec_stride, uint32_t seq_cap, const uint8_t* __restrict__ side,
+                                                                const uint64_t* __restrict__ aa_off, uint32_t L, const K* __restrict__ ref_keys,
+                                                                uint64_t n_ref, uint8_t* __restrict__ aa, uint8_t* __restrict__ flags,
+                                                                uint32_t* __restrict__ err) {
+    const uint64_t s = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (s >= n_seq) return;
+    const RowSeq rs = seq[s];
+    const uint8_t* q = (rs.flags & SRC_MERGE) ? side + rs.at
+                                              : recs + rs.at * rec_stride + 32 + ((rs.flags & SRC_GERM) ? seq_cap : 0u) + rs.off;
+    k5_sequence<K>(q, rs.len, (rs.flags & SRC_REV) != 0, L, ref_keys, n_ref, aa + aa_off[s], flags + aa_off[s], err);
 }
 
 void device_translate_records(const uint8_t* d_nt, const uint64_t* d_nt_off, const uint32_t* d_nt_len, const uint8_t* d_rev,
@@ -82,6 +109,41 @@ void device_translate_records(const uint8_t* d_nt, const uint64_t* d_nt_off, con
     else
         hipLaunchKernelGGL(k5_translate_records<unsigned __int128>, grid, block, 0, stream, d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq,
                            L, reinterpret_cast<const unsigned __int128*>(d_ref_keys), n_ref, d_aa, d_flags, d_err);
+    HIP_OK_(hipGetLastError());
+}
+
+struct RowCodons {   // scan input: codons of sequence i, 0 past the last one (the scan's extra word is the total)
+    const RowSeq* seq;
+    uint64_t n;
+    __host__ __device__ uint64_t operator()(uint64_t i) const {
+        const uint32_t len = i < n ? seq[i].len : 0;
+        return len > 2 ? (len - 2 + 2) / 3 : 0;
+    }
+};
+
+void device_row_codon_offsets(const RowSeq* d_seq, uint64_t n_seq, uint64_t* d_aa_off, hipStream_t stream) {
+    auto counts = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), RowCodons{d_seq, n_seq});
+    size_t bytes = 0;
+    HIP_OK_(rocprim::exclusive_scan(nullptr, bytes, counts, d_aa_off, uint64_t(0), size_t(n_seq + 1), rocprim::plus<uint64_t>(), stream));
+    void* d_ws = nullptr;
+    HIP_OK_(hipMalloc(&d_ws, bytes + 16));
+    hipError_t e = rocprim::exclusive_scan(d_ws, bytes, counts, d_aa_off, uint64_t(0), size_t(n_seq + 1), rocprim::plus<uint64_t>(), stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (before the scan's workspace goes)
+    (void)hipFree(d_ws);
+    HIP_OK_(e);
+}
+
+void device_translate_row_sources(const RowSeq* d_seq, uint64_t n_seq, const uint8_t* d_recs, uint32_t rec_stride, uint32_t seq_cap,
+                                  const uint8_t* d_side, const uint64_t* d_aa_off, uint32_t L, const uint64_t* d_ref_keys, uint64_t n_ref,
+                                  uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err, hipStream_t stream) {
+    if (!n_seq) return;
+    dim3 grid(uint32_t((n_seq + 255) / 256)), block(256);
+    if (key_words(L) == 1)
+        hipLaunchKernelGGL(k5_translate_row_sources<uint64_t>, grid, block, 0, stream, d_seq, n_seq, d_recs, rec_stride, seq_cap, d_side, d_aa_off,
+                           L, d_ref_keys, n_ref, d_aa, d_flags, d_err);
+    else
+        hipLaunchKernelGGL(k5_translate_row_sources<unsigned __int128>, grid, block, 0, stream, d_seq, n_seq, d_recs, rec_stride, seq_cap, d_side,
+                           d_aa_off, L, reinterpret_cast<const unsigned __int128*>(d_ref_keys), n_ref, d_aa, d_flags, d_err);
     HIP_OK_(hipGetLastError());
 }
 

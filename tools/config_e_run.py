@@ -8,10 +8,14 @@ so the exome is walked in gene chunks - exactly what the ranks of a multi-GPU ru
 per chunk normal -> FASTA -> build_reference -> sorted distinct keys; the chunks' key arrays are merged by mp_peptides_union; then
 `somatic` per chunk, shards merged by gene, and one `filter` over the merged TSV.
 
-  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--peptide-len 9] [--fused-peptidome] [--out config_e.json]
+  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--peptide-len 9] [--fused-peptidome] [--fused-filter] [--out config_e.json]
 
 (--fused-peptidome: per chunk `normal` -> Batch.peptidome, the records translated where they lie in device memory, no nucleotide
 FASTA; normal_s then includes the peptidome, build_reference_s is 0, and wall_s["fused_peptidome_s"] is the peptidome call alone)
+
+(--fused-filter: `somatic` as ONE batch over all genes, then Batch.filter against the peptidome - the rows filtered where their windows
+lie in device memory, no info.tsv; somatic_s then includes the filter, filter_s is 0, and wall_s["fused_filter_s"] is the filter call
+alone. One batch, because gene chunks would split the filter's row stream; so --skip-panics, which phases gene by gene, is refused)
 
 (--peptide-len L: windows of 3L nt in `normal` and `somatic`; 13..25 are the MHC class II lengths, with two-word peptide keys)
 """
@@ -61,8 +65,11 @@ def main():
     ap.add_argument("--peptide-len", type=int, default=9)
     ap.add_argument("--skip-panics", action="store_true", help="leave out genes the reference would panic on (phased gene by gene)")
     ap.add_argument("--fused-peptidome", action="store_true", help="normal -> peptidome on the device (Batch.peptidome), no nucleotide FASTA")
+    ap.add_argument("--fused-filter", action="store_true", help="somatic -> filter on the device (Batch.filter), no info.tsv")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.fused_filter and a.skip_panics:
+        ap.error("--fused-filter phases all genes as one batch (the filter's row stream runs over all of them); --skip-panics phases gene by gene")
     L = a.peptide_len
     ctx = m.Context(0)
     t = {}
@@ -117,28 +124,40 @@ def main():
     peptidome = ctx.peptides_union(key_arrays, L)
     t["peptides_union_s"] = time.perf_counter() - t0
     stats["peptidome_size"] = int(peptidome.keys_np.size)
-    t0 = time.perf_counter()
-    shards = []
-    som_windows = 0
-    for c in range(a.chunks):
-        genes = list(range(cuts[c], cuts[c + 1]))
-        # windows of L codons: a 27-nt window holds no 15-mer
-        for gs, _st, r in phased(ds, genes, 3 * L, m.MODE_SOMATIC, m.STREAM_ALL, a.skip_panics, skipped["somatic"]):
-            som_windows += r.windows
-            shards.append(shard_of(r, gs))
-            r.close()
-    merged = merge_by_gene(shards)
-    del shards
-    t["somatic_s"] = time.perf_counter() - t0
-    stats["somatic_windows"] = som_windows
-    stats["somatic_tsv_rows"] = merged["tsv"].count(b"\n") - 1
-    t0 = time.perf_counter()
-    f = ctx.filter(merged["tsv"], peptidome)        # the peptidome handle: its keys go to the GPU as they are
-    t["filter_s"] = time.perf_counter() - t0
+    if a.fused_filter:
+        t0 = time.perf_counter()
+        b = ds.batch(window_len=3 * L)
+        b.run()
+        tf = time.perf_counter()
+        f, _ = b.filter(peptidome)                  # the rows' windows are read in device memory: no TSV text
+        t["fused_filter_s"] = time.perf_counter() - tf
+        t["somatic_s"], t["filter_s"] = time.perf_counter() - t0, 0.0
+        b.close()
+        stats["somatic_tsv_rows"] = f.rows
+    else:
+        t0 = time.perf_counter()
+        shards = []
+        som_windows = 0
+        for c in range(a.chunks):
+            genes = list(range(cuts[c], cuts[c + 1]))
+            # windows of L codons: a 27-nt window holds no 15-mer
+            for gs, _st, r in phased(ds, genes, 3 * L, m.MODE_SOMATIC, m.STREAM_ALL, a.skip_panics, skipped["somatic"]):
+                som_windows += r.windows
+                shards.append(shard_of(r, gs))
+                r.close()
+        merged = merge_by_gene(shards)
+        del shards
+        t["somatic_s"] = time.perf_counter() - t0
+        stats["somatic_windows"] = som_windows
+        stats["somatic_tsv_rows"] = merged["tsv"].count(b"\n") - 1
+        t0 = time.perf_counter()
+        f = ctx.filter(merged["tsv"], peptidome)        # the peptidome handle: its keys go to the GPU as they are
+        t["filter_s"] = time.perf_counter() - t0
     stats.update(filter_rows=f.rows, filter_kept=f.kept, filter_removed=f.removed, filter_groups=f.groups, skipped_genes=skipped)
-    t["total_s"] = sum(v for k, v in t.items() if k not in ("generate_s", "fused_peptidome_s"))   # (the latter is inside normal_s)
+    t["total_s"] = sum(v for k, v in t.items() if k not in ("generate_s", "fused_peptidome_s", "fused_filter_s"))   # (inside normal_s / somatic_s)
     out = {"config": "E: normal + build_reference -l %d + somatic + filter, %d transcripts, %d gene chunks, one MI355X%s" %
-                     (L, a.transcripts, a.chunks, ", fused normal -> peptidome" if a.fused_peptidome else ""),
+                     (L, a.transcripts, a.chunks, (", fused normal -> peptidome" if a.fused_peptidome else "") +
+                                                        (", fused somatic -> filter" if a.fused_filter else "")),
            "wall_s": t, "stats": stats}
     print(json.dumps(out))
     if a.out:
