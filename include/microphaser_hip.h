@@ -223,6 +223,7 @@ const uint64_t* mp_peptides_keys(const mp_peptides* p, size_t* n);    /* sorted 
                                                                          exchanged in the multi-GPU peptidome union; *n = the
                                                                          number of KEYS, the array holds *n * words words */
 uint32_t mp_peptides_key_words(const mp_peptides* p);                 /* words per key: 1 or 2                */
+uint32_t mp_peptides_peptide_len(const mp_peptides* p);               /* the peptide length of the keys       */
 uint64_t mp_peptides_count(const mp_peptides* p);                     /* translated windows                   */
 void mp_peptides_free(mp_peptides* p);
 /* to_protein (reference: src/peptides.rs:128-146) for n windows of 3 * peptide_len nucleotides laid out back to back in nt;
@@ -254,6 +255,28 @@ typedef struct mp_filtered mp_filtered;
 int mp_batch_filter(mp_ctx* ctx, mp_batch* batch, const mp_peptides* reference, uint32_t streams, mp_results** results, mp_filtered** out);
 int mp_batch_filter_binary(mp_ctx* ctx, mp_batch* batch, const char* reference_binary, size_t len, uint32_t peptide_len, uint32_t streams,
                            mp_results** results, mp_filtered** out);
+
+/* The same filter over several `somatic` batches of one data set (gene chunks, batches on several contexts or devices): a filter
+ * stream takes the batches one at a time, in gene order, and ends in one filter result - byte for byte the five streams, counts and
+ * errors of mp_batch_filter on one batch of all the added genes. mp_batch_filter / mp_batch_filter_binary are create + one add +
+ * finish.
+ * create: the reference as for mp_batch_filter (a peptidome handle, which must outlive the stream) or mp_batch_filter_binary (bincode
+ *   bytes, read during the call; 1 <= peptide_len <= 25). Needs no device.
+ * add: after mp_batch_run of a MP_MODE_SOMATIC batch on ctx, the batch's own context: K5 runs on ctx's device, over the batch's
+ *   device-resident records, and the row stream advances over its rows. The batch must come from the data set of the earlier adds,
+ *   and its genes must all come after the genes added before (gaps are allowed). Checked in the order: mode, data set, gene order,
+ *   then the stream's state, then device and residency (fails like mp_batch_results if another batch ran on ctx since). streams /
+ *   results as for mp_batch_filter. The batch may be freed after the add; the data set must outlive the stream. A batch refused by
+ *   the mode, data-set or gene-order check leaves the stream as it was. Any later failure reports what mp_batch_filter would report
+ *   on the added genes, this batch's included, and ends the stream: it takes no further add or finish (its genes count as added).
+ * finish: K6 on ctx's device and the five streams. Once per stream, also on a stream without adds.
+ * Errors of each call go to the ctx passed to it. */
+typedef struct mp_filter_stream mp_filter_stream;
+int mp_filter_stream_create(mp_ctx* ctx, const mp_peptides* reference, mp_filter_stream** out);
+int mp_filter_stream_create_binary(mp_ctx* ctx, const char* reference_binary, size_t len, uint32_t peptide_len, mp_filter_stream** out);
+int mp_filter_stream_add(mp_ctx* ctx, mp_filter_stream* s, mp_batch* batch, uint32_t streams, mp_results** results);
+int mp_filter_stream_finish(mp_ctx* ctx, mp_filter_stream* s, mp_filtered** out);
+void mp_filter_stream_free(mp_filter_stream* s);
 
 /* `microphaser filter` (reference: peptides::filter, src/peptides.rs:221-709 <- run_filtering, src/main.rs:170-214,
  * src/filter_cli.yaml): translate the mutant / normal windows of a `somatic` info.tsv, drop self-similar, repeated and

@@ -189,6 +189,11 @@ def lib():
         "mp_batch_filter": (i32, [vp, vp, vp, u32, pp, pp]),
         "mp_batch_filter_binary": (i32, [vp, vp, cp, ctypes.c_size_t, u32, u32, pp, pp]),
         "mp_batch_free": (None, [vp]),
+        "mp_filter_stream_create": (i32, [vp, vp, pp]),
+        "mp_filter_stream_create_binary": (i32, [vp, cp, ctypes.c_size_t, u32, pp]),
+        "mp_filter_stream_add": (i32, [vp, vp, vp, u32, pp]),
+        "mp_filter_stream_finish": (i32, [vp, vp, pp]),
+        "mp_filter_stream_free": (None, [vp]),
         "mp_phase_dataset": (i32, [vp, vp, i32, u64, pp]),
         "mp_results_fasta": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
         "mp_results_normal_fasta": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
@@ -202,6 +207,7 @@ def lib():
         "mp_peptides_binary": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
         "mp_peptides_keys": (vp, [vp, ctypes.POINTER(ctypes.c_size_t)]),
         "mp_peptides_key_words": (u32, [vp]),
+        "mp_peptides_peptide_len": (u32, [vp]),
         "mp_key_words": (u32, [u32]),
         "mp_peptides_count": (u64, [vp]),
         "mp_peptides_free": (None, [vp]),
@@ -235,7 +241,8 @@ C_ABI_SYMBOLS = [
     "mp_synth_gene_costs", "mp_dataset_from_arrays", "mp_dataset_to_arrays", "mp_gene_batch_free", "mp_dataset_gene_costs",
     "mp_batch_create_genes", "mp_results_gene_offsets", "mp_translate", "mp_peptides_union", "mp_build_reference_buffer", "mp_peptidome_from_buffer",
     "mp_batch_results_dump", "mp_batch_results_from_dump", "mp_peptides_key_words", "mp_key_words", "mp_batch_peptidome",
-    "mp_batch_filter", "mp_batch_filter_binary",
+    "mp_batch_filter", "mp_batch_filter_binary", "mp_filter_stream_create", "mp_filter_stream_create_binary", "mp_filter_stream_add",
+    "mp_filter_stream_finish", "mp_filter_stream_free", "mp_peptides_peptide_len",
 ]
 
 
@@ -387,6 +394,7 @@ class Peptides:
         # the keys as a numpy array (a whole-exome peptidome holds ~10^7 of them): 1-D for one-word keys, (n, 2) with columns [lo, hi]
         # for two-word keys (peptide length 13..25); `.keys` gives the same as a Python list of ints on demand
         self.key_words = w = L.mp_peptides_key_words(h)
+        self.peptide_len = L.mp_peptides_peptide_len(h)
         k = np.frombuffer((ctypes.c_char * (8 * w * n.value)).from_address(p), dtype=np.uint64).copy() if n.value else np.zeros(0, dtype=np.uint64)
         self.keys_np = k if w == 1 else k.reshape(-1, 2)
         self._keys = None
@@ -580,6 +588,53 @@ class Batch:
         if self._h:
             lib().mp_batch_free(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FilterStream:
+    """`somatic` -> `filter` over several batches (mp_filter_stream_*): add() takes the `somatic` batches of one data set one at a time,
+    in gene order (gaps allowed), each right after its run(), on its own context; finish() gives the one Filtered that Batch.filter on a
+    batch of all the added genes gives. reference: a Peptides handle (its peptide length wins over peptide_len; kept alive by the
+    stream) or the bincode bytes build_reference writes. A batch refused by the mode, data-set or gene-order check leaves the stream
+    as it was; after any other failed add the stream takes no further add or finish."""
+
+    def __init__(self, ctx, reference, peptide_len=9):
+        self.ctx, self._h = ctx, None
+        self._keep = [reference]   # the handle (and the data sets of the added batches) outlive the stream
+        h = ctypes.c_void_p()
+        if isinstance(reference, Peptides):
+            ctx._check(lib().mp_filter_stream_create(ctx._h, reference._h, ctypes.byref(h)))
+        else:
+            reference = bytes(reference)
+            ctx._check(lib().mp_filter_stream_create_binary(ctx._h, reference, len(reference), peptide_len, ctypes.byref(h)))
+        self._h = h
+
+    def add(self, batch, streams=0):
+        """K5 over the batch's rows on its context's device, and the row stream over them. Returns the Results of the streams asked for
+        from the same consumer pass (as Batch.filter does), or None when streams == 0."""
+        if batch._ds not in self._keep:
+            self._keep.append(batch._ds)
+        hr = ctypes.c_void_p()
+        batch.ctx._check(lib().mp_filter_stream_add(batch.ctx._h, self._h, batch._h, streams, ctypes.byref(hr) if streams else None))
+        return Results(hr) if streams else None
+
+    def finish(self, ctx=None):
+        """K6 on ctx's device (default: the context the stream was created with) and the five streams: Filtered."""
+        ctx = ctx or self.ctx
+        hf = ctypes.c_void_p()
+        ctx._check(lib().mp_filter_stream_finish(ctx._h, self._h, ctypes.byref(hf)))
+        return Filtered(hf)
+
+    def close(self):
+        if self._h:
+            lib().mp_filter_stream_free(self._h)
+            self._h = None
+        self._keep = []
 
     def __del__(self):
         try:

@@ -2,6 +2,7 @@
 // from the per-gene inputs phase_gene would load (reference: src/microphasing.rs:895-942).
 #pragma once
 #include <deque>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -90,7 +91,9 @@ struct Batch {
     // consumer raises the message only if the real walk reaches it
     std::vector<std::pair<uint32_t, std::string>> tx_errors;
     PodVec<uint32_t> tx_max_live;         // host-only, per transcript: upper bound on its simultaneously live rows (+ pending candidates)
-    std::deque<GeneInput> split_inputs;   // the read-subset copies of deep genes (owned here: GeneHost::input points into it)
+    // the read-subset copies of deep genes (GeneHost::input points into them); shared with the filter streams whose captured rows view
+    // their text
+    std::shared_ptr<const std::deque<GeneInput>> split_inputs;
     // ---- sizing
     uint32_t seq_cap = SEQ_CAPS[0];       // HapRec sequence capacity of this batch (SEQ_CAPS)
     uint32_t mask_words = 1;              // W: u64 words of the per-read support / low-qual masks

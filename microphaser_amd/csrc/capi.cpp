@@ -154,6 +154,8 @@ int mp_batch_create(mp_ctx* ctx, const mp_dataset* ds, int mode, uint64_t window
         if (gene_lo > gene_hi) gene_lo = gene_hi;
         std::unique_ptr<mp_batch> b(new mp_batch());
         b->reads = &ds->ds.bam.reads;
+        b->ds = ds;
+        for (uint32_t g = gene_lo; g < gene_hi; g++) b->genes.push_back(g);
         build_batch(genes.data() + gene_lo, size_t(gene_hi - gene_lo), *b->reads, window_len, mode == MP_MODE_NORMAL, b->batch);
         if (std::getenv("MP_DEBUG")) {
             uint32_t mx = 0;
@@ -322,29 +324,58 @@ int mp_batch_peptidome(mp_ctx* ctx, mp_batch* batch, uint32_t peptide_len, uint3
 }  // extern "C"
 
 namespace {
-// `somatic` -> `filter` on the resident batch: the consumer captures the rows (and writes the text streams asked for), the filter reads
-// their windows where they lie in device memory. The host copy of the records stays alive until the filter is done: the captured rows'
-// sequence fields point into it.
+// `somatic` -> `filter` on the resident batch, one batch of a filter stream: the consumer captures the rows (and writes the text streams
+// asked for), the stream reads their windows where they lie in device memory. The host copy of the records (and the batch's copies of
+// split genes) stay with the stream until it is finished: the captured rows' fields point into them.
+void stream_add(mp_ctx* ctx, mp_filter_stream* s, mp_batch* batch, const char* what, uint32_t streams, mp_results** results) {
+    if (!s) throw Error(std::string(what) + ": no filter stream");
+    if (batch->batch.normal)
+        throw Error(std::string(what) + ": the batch is a normal batch - the filter reads the rows of a `somatic` run (MP_MODE_SOMATIC)");
+    if (s->ds && batch->ds != s->ds) throw Error(std::string(what) + ": the batch comes from another data set than the stream's earlier batches");
+    if (!batch->genes.empty() && int64_t(batch->genes.front()) <= s->last_gene)
+        throw Error(std::string(what) + ": gene " + std::to_string(batch->genes.front()) + " does not come after gene " +
+                    std::to_string(s->last_gene) + ", which an earlier batch added - add the batches in gene order, each gene once");
+    // (a batch refused by the checks above changes nothing. From here on the batch's genes count as added, whatever the outcome: an add
+    // that fails past this point ends the stream, which then holds a partial row stream)
+    if (s->finished) throw Error(std::string(what) + ": the stream has been finished");
+    if (s->failed) throw Error(std::string(what) + ": an earlier add on this stream failed - the stream takes no more batches; start a new one");
+    s->ds = batch->ds;
+    if (!batch->genes.empty()) s->last_gene = batch->genes.back();
+    s->failed = true;   // (until the add is through)
+    DeviceContext& dev = need_device(ctx);
+    if (!batch->ran) throw Error("mp_batch_results before mp_batch_run");
+    if (ctx->last_run != batch) throw Error("mp_batch_results: another batch has been created or run on this context since this one ran - run it again");
+    struct Held { HostResults hr; std::shared_ptr<const std::deque<GeneInput>> genes; };
+    std::shared_ptr<Held> held(new Held());
+    dev.download(held->hr);
+    held->genes = batch->batch.split_inputs;
+    std::unique_ptr<mp_results> r(new mp_results());
+    RowCapture cap;
+    consume_batch(batch->batch, held->hr, r->out, streams, &cap);
+    const RecArena arena{dev.dev_recs(), dev.rec_slots(), dev.rec_stride(), dev.seq_cap()};
+    s->stream.add_captured(dev.device(), std::move(cap), arena, std::move(held));
+    s->failed = false;
+    if (results) *results = r.release();
+}
+
+void stream_finish(mp_ctx* ctx, mp_filter_stream* s, const char* what, mp_filtered** out) {
+    if (!s) throw Error(std::string(what) + ": no filter stream");
+    if (s->finished) throw Error(std::string(what) + ": the stream has been finished already");
+    if (s->failed) throw Error(std::string(what) + ": an earlier add on this stream failed - the stream has no result; start a new one");
+    s->finished = true;   // (once, whatever the outcome)
+    DeviceContext& dev = need_device(ctx);
+    std::unique_ptr<mp_filtered> f(new mp_filtered());
+    s->stream.finish(dev.device(), f->res);
+    *out = f.release();
+}
+
 void batch_filter(mp_ctx* ctx, mp_batch* batch, const char* what, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys,
                   uint32_t peptide_len, uint32_t streams, mp_results** results, mp_filtered** out) {
     if (batch->batch.normal)
         throw Error(std::string(what) + ": the batch is a normal batch - the filter reads the rows of a `somatic` run (MP_MODE_SOMATIC)");
-    check_peptide_len(peptide_len);
-    DeviceContext& dev = need_device(ctx);
-    if (!batch->ran) throw Error("mp_batch_results before mp_batch_run");
-    if (ctx->last_run != batch) throw Error("mp_batch_results: another batch has been created or run on this context since this one ran - run it again");
-    HostResults hr;
-    dev.download(hr);
-    std::unique_ptr<mp_results> r(new mp_results());
-    RowCapture cap;
-    consume_batch(batch->batch, hr, r->out, streams, &cap);
-    std::unique_ptr<mp_filtered> f(new mp_filtered());
-    const RecArena arena{dev.dev_recs(), dev.rec_slots(), dev.rec_stride(), dev.seq_cap()};
-    filter_captured(dev.device(), reference_binary, reference_keys, cap, arena, peptide_len, f->res);
-    release_later(std::move(cap));
-    release_later(std::move(hr));
-    *out = f.release();
-    if (results) *results = r.release();
+    mp_filter_stream s(reference_binary, reference_keys, peptide_len);
+    stream_add(ctx, &s, batch, what, streams, results);
+    stream_finish(ctx, &s, what, out);
 }
 }  // namespace
 
@@ -365,6 +396,29 @@ int mp_batch_filter_binary(mp_ctx* ctx, mp_batch* batch, const char* reference_b
         batch_filter(ctx, batch, "mp_batch_filter_binary", std::string_view(reference_binary, len), nullptr, peptide_len, streams, results, out);
     });
 }
+
+int mp_filter_stream_create(mp_ctx* ctx, const mp_peptides* reference, mp_filter_stream** out) {
+    return guarded(ctx, [&] {
+        if (!reference) throw Error("mp_filter_stream_create: no peptidome");
+        *out = new mp_filter_stream(std::string_view(), &reference->res.keys, reference->res.peptide_len);
+    });
+}
+
+int mp_filter_stream_create_binary(mp_ctx* ctx, const char* reference_binary, size_t len, uint32_t peptide_len, mp_filter_stream** out) {
+    return guarded(ctx, [&] { *out = new mp_filter_stream(std::string_view(reference_binary, len), nullptr, peptide_len); });
+}
+
+int mp_filter_stream_add(mp_ctx* ctx, mp_filter_stream* s, mp_batch* batch, uint32_t streams, mp_results** results) {
+    PhaseTimer phase_timer("filter_stream_add");
+    return guarded(ctx, [&] { stream_add(ctx, s, batch, "mp_filter_stream_add", streams, results); });
+}
+
+int mp_filter_stream_finish(mp_ctx* ctx, mp_filter_stream* s, mp_filtered** out) {
+    PhaseTimer phase_timer("filter_stream_finish");
+    return guarded(ctx, [&] { stream_finish(ctx, s, "mp_filter_stream_finish", out); });
+}
+
+void mp_filter_stream_free(mp_filter_stream* s) { delete s; }
 
 void mp_batch_free(mp_batch* batch) { delete batch; }   // (a context never dereferences its resident / last_run pointers)
 
@@ -495,6 +549,7 @@ const char* mp_peptides_binary(const mp_peptides* p, size_t* len) {
 }
 const uint64_t* mp_peptides_keys(const mp_peptides* p, size_t* n) { if (n) *n = p->res.n_keys(); return p->res.keys.data(); }
 uint32_t mp_peptides_key_words(const mp_peptides* p) { return key_words(p->res.peptide_len); }
+uint32_t mp_peptides_peptide_len(const mp_peptides* p) { return p->res.peptide_len; }
 uint32_t mp_key_words(uint32_t peptide_len) { return peptide_len >= 1 && peptide_len <= MAX_PEPTIDE_LEN ? key_words(peptide_len) : 0; }
 uint64_t mp_peptides_count(const mp_peptides* p) { return p->res.n_peptides; }
 void mp_peptides_free(mp_peptides* p) { delete p; }

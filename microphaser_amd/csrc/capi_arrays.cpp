@@ -280,6 +280,8 @@ int mp_batch_create_genes(mp_ctx* ctx, const mp_dataset* ds, int mode, uint64_t 
         }
         std::unique_ptr<mp_batch> b(new mp_batch());
         b->reads = &ds->ds.bam.reads;
+        b->ds = ds;
+        b->genes.assign(list, list + n);
         build_batch(ptrs.data(), n, *b->reads, window_len, mode == MP_MODE_NORMAL, b->batch);
         if (ctx->dev) {
             ctx->resident = nullptr; ctx->last_run = nullptr;   // (an upload that throws leaves nothing resident)

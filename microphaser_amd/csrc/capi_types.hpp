@@ -25,6 +25,8 @@ struct mp_dataset {
 };
 struct mp_batch {
     Batch batch;                   // GeneHost::input points into the data set, which must outlive the batch
+    const mp_dataset* ds = nullptr;
+    std::vector<uint32_t> genes;   // the data set's ordinals of the batch's genes, ascending (a deep gene's read-subset copies: not listed)
     const ReadStore* reads = nullptr;
     bool uploaded = false, ran = false;
     RunTiming timing;
@@ -39,6 +41,14 @@ struct mp_results {
 };
 struct mp_filtered {
     FilterResult res;
+};
+struct mp_filter_stream {
+    FilterStream stream;
+    const mp_dataset* ds = nullptr;   // the data set of the adds (set by the first)
+    int64_t last_gene = -1;           // the highest gene ordinal added so far
+    bool failed = false, finished = false;
+    mp_filter_stream(std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, uint32_t peptide_len)
+        : stream(reference_binary, reference_keys, peptide_len) {}
 };
 struct mp_peptides {
     PeptideResult res;

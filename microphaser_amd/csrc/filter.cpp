@@ -276,168 +276,237 @@ struct Laps {
     }
 };
 
-// What both row sources do first: the device, and the reference peptidome - bincode v1 HashSet<Vec<u8>> (deserialize_from(...).unwrap(),
-// :242) -> keys of the length-L members; or the sorted distinct keys themselves (a peptidome that never left the library, reference_keys
-// != nullptr: ref_keys stays empty). Keys of key_words(L) words each (pep.hpp).
-void filter_begin(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, uint32_t L, FilterResult& out,
-                  std::vector<uint64_t>& ref_keys, Laps& lap) {
-    check_peptide_len(L);
-    const uint32_t w = key_words(L);
-    out = FilterResult();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        throw Error("no HIP device available: `filter` translates and scores on the GPU, there is no CPU fallback");
-    HIP_OK(hipSetDevice(device));
-    if (!reference_keys) {
-        size_t p = 0;
-        auto u64 = [&]() {
-            if (p + 8 > reference_binary.size())
-                throw Error("reference would panic: called `Result::unwrap()` on an `Err` value (bincode: unexpected end of file)");
-            uint64_t v = 0;
-            for (int i = 0; i < 8; i++) v |= uint64_t(uint8_t(reference_binary[p + i])) << (8 * i);
-            p += 8;
-            return v;
-        };
-        const uint64_t n = u64();
-        for (uint64_t i = 0; i < n; i++) {
-            const uint64_t l = u64();
-            if (l > reference_binary.size() - p)
-                throw Error("reference would panic: called `Result::unwrap()` on an `Err` value (bincode: unexpected end of file)");
-            if (l == L) {  // only a member of the same length can equal a tumor peptide
-                bool letters = true;
-                for (uint64_t k = 0; k < l; k++) { const char c = reference_binary[p + k]; letters &= c >= 'A' && c <= 'Z'; }
-                if (letters) push_key(ref_keys, peptide_to_key(reference_binary.data() + p, l), w);
-            }
-            p += l;
-        }
+// A stream on one device with the device memory of one step: everything is released when the step ends, whether it throws or not
+struct DeviceStep {
+    hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    std::vector<void*> owned;
+    DeviceStep() {
+        HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
     }
-    lap("reference set decoded");
+    ~DeviceStep() {
+        for (void* p : owned) (void)hipFree(p);
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        (void)hipStreamDestroy(stream);
+    }
+    template <class T> T* alloc(size_t bytes) {
+        void* p = nullptr;
+        HIP_OK(hipMalloc(&p, bytes));
+        owned.push_back(p);
+        return static_cast<T*>(p);
+    }
+};
+
+// The reference peptidome - bincode v1 HashSet<Vec<u8>> (deserialize_from(...).unwrap(), :242) -> keys of the length-L members, of
+// key_words(L) words each (pep.hpp)
+void decode_reference(std::string_view reference_binary, uint32_t L, std::vector<uint64_t>& ref_keys) {
+    const uint32_t w = key_words(L);
+    size_t p = 0;
+    auto u64 = [&]() {
+        if (p + 8 > reference_binary.size())
+            throw Error("reference would panic: called `Result::unwrap()` on an `Err` value (bincode: unexpected end of file)");
+        uint64_t v = 0;
+        for (int i = 0; i < 8; i++) v |= uint64_t(uint8_t(reference_binary[p + i])) << (8 * i);
+        p += 8;
+        return v;
+    };
+    const uint64_t n = u64();
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t l = u64();
+        if (l > reference_binary.size() - p)
+            throw Error("reference would panic: called `Result::unwrap()` on an `Err` value (bincode: unexpected end of file)");
+        if (l == L) {  // only a member of the same length can equal a tumor peptide
+            bool letters = true;
+            for (uint64_t k = 0; k < l; k++) { const char c = reference_binary[p + k]; letters &= c >= 'A' && c <= 'Z'; }
+            if (letters) push_key(ref_keys, peptide_to_key(reference_binary.data() + p, l), w);
+        }
+        p += l;
+    }
 }
 
-// The common part of both row sources: the reference keys sorted on the device, K5, then the row stream, K6 and the emission. The
-// source supplies the rows (in TSV order) and K5 in two steps: offsets(stream, owned) fills aa_off (n_seq + 1 entries: sequence s =
-// 2r mutant, 2r + 1 normal of row r) and returns it on the device; launch(stream, d_aa_off, d_ref, n_ref, d_aa, d_flags, d_err) enqueues
-// the translation.
-template <class Offsets, class Launch>
-void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64_t>& ref_keys, uint32_t L, const RowVec& rows,
-                 PodVec<uint64_t>& aa_off, Offsets offsets, Launch launch, Laps& lap, FilterResult& out) {
-    const uint32_t w = key_words(L);
-    const size_t threads = host_threads();
-    out.n_rows = rows.size();
-    hipStream_t stream;
-    HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    hipEvent_t e0, e1, e2, e3;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2)); HIP_OK(hipEventCreate(&e3));
-    std::vector<void*> owned;
-    auto cleanup = [&] {
-        for (void* p : owned) hipFree(p);
-        owned.clear();
-        hipEventDestroy(e0); hipEventDestroy(e1); hipEventDestroy(e2); hipEventDestroy(e3);
-        hipStreamDestroy(stream);
+// ---- the row stream (:262-563): which (row, i) peptides survive, and the groups they are scored in
+struct Entry { uint32_t chunk; uint32_t row; uint32_t i1; uint32_t normal_len; uint64_t tumor_at; const uint8_t* normal_pep; uint64_t group; };
+// records / frequencies / depth of the current region, by (frame, somatic_positions, germline_positions): the reference's BTreeMaps.
+// A region holds a few keys; the slots keep their buffers from region to region and are put in key order when the region is flushed
+struct Key {
+    uint64_t frame; std::string_view som, germ;
+    bool operator==(const Key& o) const { return frame == o.frame && som == o.som && germ == o.germ; }
+    bool operator<(const Key& o) const { return std::tie(frame, som, germ) < std::tie(o.frame, o.som, o.germ); }
+};
+struct Pending { Key key; std::vector<double> alt; std::vector<uint32_t> depth; std::vector<Entry> recs; };
+
+}  // namespace
+
+struct FilterStream::State {
+    uint32_t L, w;
+    const std::vector<uint64_t>* reference_keys;
+    std::vector<uint64_t> ref_keys;   // the decoded bincode members (unsorted; empty with reference_keys)
+    std::string ref_error;            // a bincode image that does not decode: reported where the one-part filter reports it
+    struct DevRef { int device; uint64_t* keys; uint64_t n; };   // the sorted distinct reference keys on one device
+    std::vector<DevRef> dev_refs;
+    // one part of the row stream: its rows (and what their views point into), their amino acids and K5's flags
+    struct Chunk {
+        RowCapture cap;                      // (a TSV's rows are in cap.rows; its quoted fields in `quoted`)
+        std::deque<std::string> quoted;
+        std::shared_ptr<const void> hold;
+        PodVec<uint8_t> aa, flags;
+        PodVec<uint64_t> aa_off;             // n_seq + 1 entries: sequence 2r mutant, 2r + 1 normal of row r
     };
-    try {
-        // sorted distinct reference keys (device radix sort + unique, unless they came sorted)
-        uint64_t n_ref = 0;
-        uint64_t* d_ref = nullptr;
+    std::vector<std::unique_ptr<Chunk>> chunks;
+    uint64_t n_rows = 0;
+    float translate_ms = 0;
+    // ---- the row stream's state, carried from one part to the next
+    std::vector<Entry> entries;                 // in output order
+    std::vector<uint64_t> grp_off{0};
+    std::vector<uint8_t> grp_final;
+    std::vector<double> g_alt;
+    std::vector<uint32_t> g_depth;
+    std::vector<Pending> slots;
+    size_t n_used = 0;
+    std::map<Key, size_t> slot_index;           // only for a region with more keys than a scan should look through
+    static constexpr size_t SCAN_LIMIT = 12;
+    std::vector<size_t> order;
+    // `current` (transcript, somatic_positions, germline_positions) and `region_sites` (transcript, variant_sites) of the reference are
+    // kept as the row that last set them; both start as tuples of empty strings
+    const Row* current = &empty_row();
+    const Row* region = &empty_row();
+    SeenPeptides seen_peptides;
+    // stop_gained: (transcript, frame) -> offset of the stop-gain row. Rows come in runs of one (transcript, frame), so the entry
+    // of the previous row is remembered.
+    std::map<std::pair<std::string_view, uint64_t>, size_t> stop_gained;
+    const Row* sg_row = nullptr;                // the row the remembered look-up was made for
+    size_t* sg_at = nullptr;                    // its entry (nullptr: none)
+
+    static const Row& empty_row() { static const Row r{}; return r; }
+
+    ~State() { free_references(); }
+
+    void free_references() {
+        if (dev_refs.empty()) return;   // (a stream that never reached a device makes no HIP call)
+        int cur = -1;
+        const bool restore = hipGetDevice(&cur) == hipSuccess;
+        for (const DevRef& r : dev_refs)
+            if (r.keys && hipSetDevice(r.device) == hipSuccess) (void)hipFree(r.keys);
+        if (restore) (void)hipSetDevice(cur);
+        dev_refs.clear();
+    }
+
+    // What every add and finish does first: the device, and the reference (its decoding error, if any)
+    void begin(int device) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+            throw Error("no HIP device available: `filter` translates and scores on the GPU, there is no CPU fallback");
+        HIP_OK(hipSetDevice(device));
+        if (!ref_error.empty()) throw Error(ref_error);
+    }
+
+    // The sorted distinct reference keys on `device`: uploaded (and, decoded from bincode, radix-sorted + de-duplicated) on first use
+    const DevRef& reference_on(int device) {
+        for (const DevRef& r : dev_refs) if (r.device == device) return r;
+        DevRef r{device, nullptr, 0};
+        DeviceStep st;
         if (reference_keys) {
-            n_ref = reference_keys->size() / w;
-            if (n_ref) d_ref = to_device(*reference_keys, stream, owned);
+            r.n = reference_keys->size() / w;
+            if (r.n) {
+                r.keys = to_device(*reference_keys, st.stream, st.owned);
+                st.owned.pop_back();   // (kept: freed by ~State)
+            }
         } else if (!ref_keys.empty()) {
-            uint64_t* d_in = to_device(ref_keys, stream, owned);
-            void *d_tmp = nullptr, *d_out = nullptr;
-            HIP_OK(hipMalloc(&d_tmp, ref_keys.size() * 8)); owned.push_back(d_tmp);
-            HIP_OK(hipMalloc(&d_out, ref_keys.size() * 8)); owned.push_back(d_out);
-            n_ref = device_sort_unique(d_in, static_cast<uint64_t*>(d_tmp), static_cast<uint64_t*>(d_out), ref_keys.size() / w, L, stream);
-            d_ref = static_cast<uint64_t*>(d_out);
+            uint64_t* d_in = to_device(ref_keys, st.stream, st.owned);
+            uint64_t* d_tmp = st.alloc<uint64_t>(ref_keys.size() * 8);
+            void* d_out = nullptr;
+            HIP_OK(hipMalloc(&d_out, ref_keys.size() * 8));
+            r.keys = static_cast<uint64_t*>(d_out);
+            try { r.n = device_sort_unique(d_in, d_tmp, r.keys, ref_keys.size() / w, L, st.stream); }
+            catch (...) { (void)hipFree(d_out); throw; }
         }
-        // ---- K5
-        const uint64_t* d_aa_off = offsets(stream, owned);
-        const uint64_t n_aa = aa_off[rows.size() * 2];
-        void *d_aa = nullptr, *d_flags = nullptr, *d_err = nullptr;
-        HIP_OK(hipMalloc(&d_aa, n_aa + 16)); owned.push_back(d_aa);
-        HIP_OK(hipMalloc(&d_flags, n_aa + 16)); owned.push_back(d_flags);
-        HIP_OK(hipMalloc(&d_err, 4)); owned.push_back(d_err);
-        HIP_OK(hipMemsetAsync(d_err, 0, 4, stream));
-        HIP_OK(hipMemsetAsync(d_flags, 0, n_aa + 16, stream));
-        HIP_OK(hipEventRecord(e0, stream));
-        launch(stream, d_aa_off, d_ref, n_ref, static_cast<uint8_t*>(d_aa), static_cast<uint8_t*>(d_flags), static_cast<uint32_t*>(d_err));
-        HIP_OK(hipEventRecord(e1, stream));
-        PodVec<uint8_t> aa(n_aa), flags(n_aa);
+        try { HIP_OK(hipStreamSynchronize(st.stream)); }
+        catch (...) { if (r.keys) (void)hipFree(r.keys); throw; }
+        dev_refs.push_back(r);
+        return dev_refs.back();
+    }
+
+    // K5 over the rows of chunk c on `device`, in two steps supplied by its source: offsets(stream, owned) fills c.aa_off and returns it on
+    // the device; launch(stream, d_aa_off, d_ref, n_ref, d_aa, d_flags, d_err) enqueues the translation. Returns K5's error word.
+    template <class Offsets, class Launch>
+    uint32_t translate(int device, Chunk& c, Offsets offsets, Launch launch) {
+        const DevRef& ref = reference_on(device);
+        DeviceStep st;
+        const uint64_t* d_aa_off = offsets(st.stream, st.owned);
+        const uint64_t n_aa = c.aa_off[c.cap.rows.size() * 2];
+        uint8_t* d_aa = st.alloc<uint8_t>(n_aa + 16);
+        uint8_t* d_flags = st.alloc<uint8_t>(n_aa + 16);
+        uint32_t* d_err = st.alloc<uint32_t>(4);
+        HIP_OK(hipMemsetAsync(d_err, 0, 4, st.stream));
+        HIP_OK(hipMemsetAsync(d_flags, 0, n_aa + 16, st.stream));
+        HIP_OK(hipEventRecord(st.e0, st.stream));
+        launch(st.stream, d_aa_off, ref.keys, ref.n, d_aa, d_flags, d_err);
+        HIP_OK(hipEventRecord(st.e1, st.stream));
+        c.aa.resize(n_aa);
+        c.flags.resize(n_aa);
         uint32_t err = 0;
         if (n_aa) {
-            HIP_OK(hipMemcpyAsync(aa.data(), d_aa, n_aa, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipMemcpyAsync(flags.data(), d_flags, n_aa, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipMemcpyAsync(c.aa.data(), d_aa, n_aa, hipMemcpyDeviceToHost, st.stream));
+            HIP_OK(hipMemcpyAsync(c.flags.data(), d_flags, n_aa, hipMemcpyDeviceToHost, st.stream));
         }
-        HIP_OK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(hipEventElapsedTime(&out.translate_ms, e0, e1));
-        lap("reference sort + K5 + copies");
+        HIP_OK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st.stream));
+        HIP_OK(hipStreamSynchronize(st.stream));
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, st.e0, st.e1));
+        translate_ms += ms;
+        return err;
+    }
 
-        // ---- the row stream (:262-563): which (row, i) peptides survive, and the groups they are scored in
-        struct Entry { uint32_t row; uint32_t i1; uint64_t tumor_at; const uint8_t* normal_pep; uint32_t normal_len; uint64_t group; };
-        std::vector<Entry> entries;                 // in output order
-        std::vector<uint64_t> grp_off{0};
-        std::vector<uint8_t> grp_final;
-        std::vector<double> g_alt;
-        std::vector<uint32_t> g_depth;
-        entries.reserve(rows.size());
-        // records / frequencies / depth of the current region, by (frame, somatic_positions, germline_positions): the reference's BTreeMaps.
-        // A region holds a few keys; the slots keep their buffers from region to region and are put in key order when the region is flushed
-        struct Key {
-            uint64_t frame; std::string_view som, germ;
-            bool operator==(const Key& o) const { return frame == o.frame && som == o.som && germ == o.germ; }
-            bool operator<(const Key& o) const { return std::tie(frame, som, germ) < std::tie(o.frame, o.som, o.germ); }
-        };
-        struct Pending { Key key; std::vector<double> alt; std::vector<uint32_t> depth; std::vector<Entry> recs; };
-        std::vector<Pending> slots;
-        size_t n_used = 0;
-        std::map<Key, size_t> slot_index;           // only for a region with more keys than a scan should look through
-        constexpr size_t SCAN_LIMIT = 12;
-        auto find_slot = [&](const Key& k) -> Pending* {
-            if (n_used > SCAN_LIMIT) {
-                auto it = slot_index.find(k);
-                return it == slot_index.end() ? nullptr : &slots[it->second];
-            }
-            for (size_t i = 0; i < n_used; i++) if (slots[i].key == k) return &slots[i];
-            return nullptr;
-        };
-        auto add_slot = [&](const Key& k) -> Pending& {
-            if (n_used == slots.size()) slots.emplace_back();
-            Pending& p = slots[n_used];
-            p.key = k; p.alt.clear(); p.depth.clear(); p.recs.clear();
-            n_used++;
-            if (n_used == SCAN_LIMIT + 1) for (size_t i = 0; i + 1 < n_used; i++) slot_index[slots[i].key] = i;
-            if (n_used > SCAN_LIMIT) slot_index[k] = n_used - 1;
-            return p;
-        };
-        std::vector<size_t> order;
-        auto flush = [&](bool final_pass) {
-            order.resize(n_used);
-            for (size_t i = 0; i < n_used; i++) order[i] = i;
-            if (n_used > 1) std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return slots[a].key < slots[b].key; });
-            for (size_t i : order) {
-                Pending& p = slots[i];
-                const uint64_t g = grp_final.size();
-                grp_final.push_back(final_pass ? 1 : 0);
-                g_alt.insert(g_alt.end(), p.alt.begin(), p.alt.end());
-                g_depth.insert(g_depth.end(), p.depth.begin(), p.depth.end());
-                grp_off.push_back(g_alt.size());
-                for (Entry& e : p.recs) { e.group = g; entries.push_back(e); }
-            }
-            n_used = 0;
-            slot_index.clear();
-        };
-        // `current` (transcript, somatic_positions, germline_positions) and `region_sites` (transcript, variant_sites) of the reference are
-        // kept as the row that last set them; both start as tuples of empty strings
-        static const Row kEmptyRow{};
-        const Row* current = &kEmptyRow;
-        const Row* region = &kEmptyRow;
-        SeenPeptides seen_peptides;
-        // stop_gained: (transcript, frame) -> offset of the stop-gain row. Rows come in runs of one (transcript, frame), so the entry
-        // of the previous row is remembered.
-        std::map<std::pair<std::string_view, uint64_t>, size_t> stop_gained;
-        const Row* sg_row = nullptr;                // the row the remembered look-up was made for
-        size_t* sg_at = nullptr;                    // its entry (nullptr: none)
+    Pending* find_slot(const Key& k) {
+        if (n_used > SCAN_LIMIT) {
+            auto it = slot_index.find(k);
+            return it == slot_index.end() ? nullptr : &slots[it->second];
+        }
+        for (size_t i = 0; i < n_used; i++) if (slots[i].key == k) return &slots[i];
+        return nullptr;
+    }
+    Pending& add_slot(const Key& k) {
+        if (n_used == slots.size()) slots.emplace_back();
+        Pending& p = slots[n_used];
+        p.key = k; p.alt.clear(); p.depth.clear(); p.recs.clear();
+        n_used++;
+        if (n_used == SCAN_LIMIT + 1) for (size_t i = 0; i + 1 < n_used; i++) slot_index[slots[i].key] = i;
+        if (n_used > SCAN_LIMIT) slot_index[k] = n_used - 1;
+        return p;
+    }
+    void flush(bool final_pass) {
+        order.resize(n_used);
+        for (size_t i = 0; i < n_used; i++) order[i] = i;
+        if (n_used > 1) std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return slots[a].key < slots[b].key; });
+        for (size_t i : order) {
+            Pending& p = slots[i];
+            const uint64_t g = grp_final.size();
+            grp_final.push_back(final_pass ? 1 : 0);
+            g_alt.insert(g_alt.end(), p.alt.begin(), p.alt.end());
+            g_depth.insert(g_depth.end(), p.depth.begin(), p.depth.end());
+            grp_off.push_back(g_alt.size());
+            for (Entry& e : p.recs) { e.group = g; entries.push_back(e); }
+        }
+        n_used = 0;
+        slot_index.clear();
+    }
+
+    // The row stream over the rows of chunk ci (translated; err: K5's error word), continuing where the previous chunk left it
+    void advance(uint32_t ci, uint32_t err) {
+        const Chunk& c = *chunks[ci];
+        const RowVec& rows = c.cap.rows;
+        const PodVec<uint64_t>& aa_off = c.aa_off;
+        n_rows += rows.size();
+        if (entries.capacity() < entries.size() + rows.size())   // (geometric: a stream of many small parts must not copy them all each time)
+            entries.reserve(std::max(2 * entries.capacity(), entries.size() + rows.size()));
+        // the hot members as locals, stored back after the last row: the loop's stores through vectors would otherwise make the compiler
+        // load them again for every peptide
+        const uint32_t L = this->L;
+        const Row* current = this->current;
+        const Row* region = this->region;
+        const Row* sg_row = this->sg_row;
+        size_t* sg_at = this->sg_at;
         for (size_t r = 0; r < rows.size(); r++) {
             const Row& row = rows[r];
             if (row.mutant_sequence.size() < 2 || (!row.normal_sequence.empty() && row.normal_sequence.size() < 2))  // `r.len() - 2` (:139)
@@ -451,9 +520,9 @@ void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64
                 som_pos = size_t(v);
             }
             const size_t offset = size_t(row.offset);
-            const uint8_t* tp = aa.data() + aa_off[2 * r];
+            const uint8_t* tp = c.aa.data() + aa_off[2 * r];
             const size_t tlen = size_t(aa_off[2 * r + 1] - aa_off[2 * r]);
-            const uint8_t* np = aa.data() + aa_off[2 * r + 1];
+            const uint8_t* np = c.aa.data() + aa_off[2 * r + 1];
             const size_t nlen = size_t(aa_off[2 * r + 2] - aa_off[2 * r + 1]);
             if (err & 1)   // some codon held a base other than A, C, G, T: find the first row it is in
                 for (size_t k = 0; k < tlen + nlen; k++)
@@ -475,7 +544,7 @@ void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64
                 if (sg_at) *sg_at = offset;
                 else sg_at = &(stop_gained[{row.transcript, row.frame}] = offset);
             }
-            const uint8_t* tf = flags.data() + aa_off[2 * r];
+            const uint8_t* tf = c.flags.data() + aa_off[2 * r];
             size_t i = 0;
             while (i + L <= tlen) {
                 if (tf[i] & 1) break;  // the peptide contains a stop (:330-332)
@@ -501,7 +570,7 @@ void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64
                     seen_peptides.clear();
                 }
                 seen_peptides.insert(tumor_pep);
-                const Entry e{uint32_t(r), uint32_t(i), aa_off[2 * r] + i0, npep, uint32_t(nl), 0};
+                const Entry e{ci, uint32_t(r), uint32_t(i), uint32_t(nl), aa_off[2 * r] + i0, npep, 0};
                 const Key key{row.frame, row.somatic_positions, row.germline_positions};
                 const double alt = row.freq * double(row.depth);
                 if (row.transcript != region->transcript || row.variant_sites != region->variant_sites) {  // :398-541
@@ -517,8 +586,22 @@ void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64
                 }
             }
         }
+        this->current = current;
+        this->region = region;
+        this->sg_row = sg_row;
+        this->sg_at = sg_at;
+    }
+
+    // The last region (:541), K6 on `device`, and the emission (:483-533, :662-706)
+    void finish(int device, FilterResult& out) {
+        Laps lap;
+        begin(device);
+        out = FilterResult();
+        const size_t threads = host_threads();
         flush(true);
-        lap("row stream");
+        lap("row stream: last region");
+        out.n_rows = n_rows;
+        out.translate_ms = translate_ms;
         out.n_peptides = entries.size();
         out.n_groups = grp_final.size();
 
@@ -531,23 +614,23 @@ void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64
                 ln_fact[0] = std::log(1.0);
                 for (int k = 1; k < 171; k++) { f *= double(k); ln_fact[k] = std::log(f); }
             }
-            uint64_t* d_goff = to_device(grp_off, stream, owned);
-            uint8_t* d_gfin = to_device(grp_final, stream, owned);
-            double* d_alt = to_device(g_alt, stream, owned);
-            uint32_t* d_dep = to_device(g_depth, stream, owned);
-            double* d_lf = to_device(ln_fact, stream, owned);
-            void* d_ci = nullptr;
-            HIP_OK(hipMalloc(&d_ci, ci.size() * sizeof(CredibleInterval))); owned.push_back(d_ci);
-            HIP_OK(hipEventRecord(e2, stream));
-            device_credible_intervals(d_goff, d_gfin, d_alt, d_dep, ci.size(), d_lf, static_cast<CredibleInterval*>(d_ci), stream);
-            HIP_OK(hipEventRecord(e3, stream));
-            HIP_OK(hipMemcpyAsync(ci.data(), d_ci, ci.size() * sizeof(CredibleInterval), hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
-            HIP_OK(hipEventElapsedTime(&out.stats_ms, e2, e3));
+            DeviceStep st;
+            uint64_t* d_goff = to_device(grp_off, st.stream, st.owned);
+            uint8_t* d_gfin = to_device(grp_final, st.stream, st.owned);
+            double* d_alt = to_device(g_alt, st.stream, st.owned);
+            uint32_t* d_dep = to_device(g_depth, st.stream, st.owned);
+            double* d_lf = to_device(ln_fact, st.stream, st.owned);
+            CredibleInterval* d_ci = st.alloc<CredibleInterval>(ci.size() * sizeof(CredibleInterval));
+            HIP_OK(hipEventRecord(st.e0, st.stream));
+            device_credible_intervals(d_goff, d_gfin, d_alt, d_dep, ci.size(), d_lf, d_ci, st.stream);
+            HIP_OK(hipEventRecord(st.e1, st.stream));
+            HIP_OK(hipMemcpyAsync(ci.data(), d_ci, ci.size() * sizeof(CredibleInterval), hipMemcpyDeviceToHost, st.stream));
+            HIP_OK(hipStreamSynchronize(st.stream));
+            HIP_OK(hipEventElapsedTime(&out.stats_ms, st.e0, st.e1));
         }
         lap("K6 credible intervals");
 
-        // ---- emission (:483-533, :662-706): the entries in order, written by all host threads (entry ranges) and joined
+        // ---- emission: the entries in order, written by all host threads (entry ranges) and joined
         for (const Entry& e : entries)
             if (ci[e.group].status) throw Error("reference would panic: called `Option::unwrap()` on a `None` value (partial_cmp of a NaN likelihood)");
         struct Streams { TextBuf tsv, removed_tsv, fasta, normal_fasta, removed_fasta; uint64_t kept = 0, removed = 0; };
@@ -558,25 +641,30 @@ void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64
             const size_t lo = entries.size() * t / parts, hi = entries.size() * (t + 1) / parts;
             o.tsv.reserve((hi - lo) * 320);
             std::string id;
+            const Chunk* cp = nullptr;
+            uint32_t c_at = 0xFFFFFFFFu;
             for (size_t k = lo; k < hi; k++) {
                 const Entry& e = entries[k];
-                const Row& row = rows[e.row];
-                const CredibleInterval& c = ci[e.group];
+                if (e.chunk != c_at) { c_at = e.chunk; cp = chunks[c_at].get(); }   // (entries come chunk by chunk)
+                const Chunk& c = *cp;
+                const Row& row = c.cap.rows[e.row];
+                const CredibleInterval& g = ci[e.group];
                 char buf[64];
-                std::snprintf(buf, sizeof buf, "%.2f-%.2f", c.a, c.b);
+                std::snprintf(buf, sizeof buf, "%.2f-%.2f", g.a, g.b);
                 id.clear();
                 append_u64(id, e.i1);
                 id.push_back('_');
                 id.append(row.id.data(), row.id.size());
-                const double freq = row.depth == 0 ? 0.0 : double(c.ml) * 0.01;
-                const std::string_view tumor_pep(reinterpret_cast<const char*>(aa.data() + e.tumor_at), L);
+                const double freq = row.depth == 0 ? 0.0 : double(g.ml) * 0.01;
+                const uint8_t* tumor = c.aa.data() + e.tumor_at;
+                const std::string_view tumor_pep(reinterpret_cast<const char*>(tumor), L);
                 const std::string_view normal_pep(reinterpret_cast<const char*>(e.normal_pep), e.normal_len);
-                if (flags[e.tumor_at] & 2) {
-                    put_fasta(o.removed_fasta, id, aa.data() + e.tumor_at, L);
+                if (c.flags[e.tumor_at] & 2) {
+                    put_fasta(o.removed_fasta, id, tumor, L);
                     write_filtered_record(o.removed_tsv, row, freq, id, buf, normal_pep, tumor_pep);
                     o.removed++;
                 } else {
-                    put_fasta(o.fasta, id, aa.data() + e.tumor_at, L);
+                    put_fasta(o.fasta, id, tumor, L);
                     if (e.normal_len) put_fasta(o.normal_fasta, id, e.normal_pep, e.normal_len);
                     write_filtered_record(o.tsv, row, freq, id, buf, normal_pep, tumor_pep);
                     o.kept++;
@@ -603,28 +691,90 @@ void filter_rows(const std::vector<uint64_t>* reference_keys, std::vector<uint64
         join(out.normal_fasta, &Streams::normal_fasta, false);
         join(out.removed_fasta, &Streams::removed_fasta, false);
         lap("emission");
-    } catch (...) {
-        cleanup();
-        throw;
+        // Nothing is read any more. The row stream's own state and the reference keys go first, here (as the one-call filter freed its
+        // locals); then the parts' rows and downloaded records go to the reaper thread - unmapped while this thread unmaps too, they
+        // would contend for the same lock
+        std::vector<Entry>().swap(entries);
+        std::vector<Pending>().swap(slots);
+        std::vector<double>().swap(g_alt);
+        std::vector<uint32_t>().swap(g_depth);
+        std::vector<uint64_t>().swap(grp_off);
+        std::vector<uint8_t>().swap(grp_final);
+        stop_gained.clear();
+        seen_peptides.clear();
+        free_references();
+        release_later(std::move(chunks));
     }
-    cleanup();
+};
+
+FilterStream::FilterStream(std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, uint32_t L) : s(new State()) {
+    check_peptide_len(L);
+    s->L = L;
+    s->w = key_words(L);
+    s->reference_keys = reference_keys;
+    if (!reference_keys) {
+        try { decode_reference(reference_binary, L, s->ref_keys); }
+        catch (const std::exception& e) { s->ref_error = e.what(); s->ref_keys.clear(); }
+    }
 }
 
-}  // namespace
+FilterStream::~FilterStream() = default;
 
-void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
-                   uint32_t L, FilterResult& out) {
+void FilterStream::add_captured(int device, RowCapture&& cap, const RecArena& arena, std::shared_ptr<const void> hold) {
     Laps lap;
-    std::vector<uint64_t> ref_keys;
-    filter_begin(device, reference_binary, reference_keys, L, out, ref_keys, lap);
+    s->begin(device);
+    // every sequence must lie inside what it names: K5 reads [off, off + len) of a record's half, or [at, at + len) of the side buffer
+    const size_t n_seq = cap.rows.size() * 2;
+    if (cap.seq.size() != n_seq) throw Error("internal error: captured rows and sequences disagree");
+    for (const RowSeq& rs : cap.seq) {
+        const bool ok = (rs.flags & SRC_MERGE) ? (rs.at <= cap.side.size() && rs.len <= cap.side.size() - rs.at)
+                                               : (rs.len == 0 || (rs.at < arena.n_slots && uint64_t(rs.off) + rs.len <= arena.seq_cap));
+        if (!ok) throw Error("internal error: captured sequence outside the record arena");
+    }
+    if (n_seq && !arena.recs) throw Error("internal error: no device record arena");
+    std::unique_ptr<State::Chunk> c(new State::Chunk());
+    c->cap = std::move(cap);
+    c->hold = std::move(hold);
+    c->aa_off.resize(n_seq + 1);
+    c->aa_off[0] = 0;
+    lap("captured rows checked");
+    const RowSeq* d_seq = nullptr;
+    const uint8_t* d_side = nullptr;
+    State::Chunk& C = *c;
+    const uint32_t err = s->translate(device, C,
+        [&](hipStream_t stream, std::vector<void*>& owned) -> const uint64_t* {
+            d_seq = to_device(C.cap.seq, stream, owned);
+            d_side = to_device(C.cap.side, stream, owned);
+            uint64_t* d_aa_off = nullptr;
+            HIP_OK(hipMalloc(&d_aa_off, (n_seq + 1) * 8)); owned.push_back(d_aa_off);
+            device_row_codon_offsets(d_seq, n_seq, d_aa_off, stream);
+            HIP_OK(hipMemcpyAsync(C.aa_off.data(), d_aa_off, (n_seq + 1) * 8, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            return d_aa_off;
+        },
+        [&](hipStream_t stream, const uint64_t* d_aa_off, const uint64_t* d_ref, uint64_t n_ref, uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err) {
+            device_translate_row_sources(d_seq, n_seq, arena.recs, arena.rec_stride, arena.seq_cap, d_side, d_aa_off, s->L, d_ref, n_ref, d_aa,
+                                         d_flags, d_err, stream);
+        });
+    lap("reference + K5 + copies");
+    s->chunks.push_back(std::move(c));
+    s->advance(uint32_t(s->chunks.size() - 1), err);
+    lap("row stream");
+}
+
+void FilterStream::add_text(int device, std::string_view tsv_text) {
+    Laps lap;
+    s->begin(device);
+    std::unique_ptr<State::Chunk> c(new State::Chunk());
     // ---- rows and their two nucleotide windows, laid out back to back for the upload
-    RowVec rows;
-    std::deque<std::string> arena;
-    parse_tsv(tsv_text, rows, arena);
+    RowVec& rows = c->cap.rows;
+    parse_tsv(tsv_text, rows, c->quoted);
     lap("tsv parsed");
     const size_t n_seq = rows.size() * 2;   // 2r = mutant, 2r + 1 = normal
     PodVec<uint8_t> nt, rev(n_seq);
-    PodVec<uint64_t> nt_off(n_seq), aa_off(n_seq + 1);
+    PodVec<uint64_t> nt_off(n_seq);
+    PodVec<uint64_t>& aa_off = c->aa_off;
+    aa_off.resize(n_seq + 1);
     PodVec<uint32_t> nt_len(n_seq);
     aa_off[0] = 0;
     {
@@ -633,13 +783,13 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
             const uint8_t rv = (!rows[r].id.empty() && rows[r].id.back() == 'F') ? 0 : 1;  // :291-294
             const std::string_view seqs[2] = {rows[r].mutant_sequence, rows[r].normal_sequence};
             for (int k = 0; k < 2; k++) {
-                const size_t s = 2 * r + k;
+                const size_t q = 2 * r + k;
                 if (seqs[k].size() > 0xFFFFFFFFull) throw Error("sequence too long");
-                nt_off[s] = at;
-                nt_len[s] = uint32_t(seqs[k].size());
-                rev[s] = rv;
+                nt_off[q] = at;
+                nt_len[q] = uint32_t(seqs[k].size());
+                rev[q] = rv;
                 at += seqs[k].size();
-                aa_off[s + 1] = aa_off[s] + (seqs[k].size() > 2 ? (seqs[k].size() - 2 + 2) / 3 : 0);
+                aa_off[q + 1] = aa_off[q] + (seqs[k].size() > 2 ? (seqs[k].size() - 2 + 2) / 3 : 0);
             }
         }
         nt.resize(at);
@@ -657,7 +807,7 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
     const uint64_t* d_nt_off = nullptr;
     const uint32_t* d_nt_len = nullptr;
     const uint8_t* d_rev = nullptr;
-    filter_rows(reference_keys, ref_keys, L, rows, aa_off,
+    const uint32_t err = s->translate(device, *c,
         [&](hipStream_t stream, std::vector<void*>& owned) -> const uint64_t* {
             d_nt = to_device(nt, stream, owned, 64);
             d_nt_off = to_device(nt_off, stream, owned);
@@ -666,46 +816,21 @@ void filter_device(int device, std::string_view reference_binary, const std::vec
             return to_device(aa_off, stream, owned);
         },
         [&](hipStream_t stream, const uint64_t* d_aa_off, const uint64_t* d_ref, uint64_t n_ref, uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err) {
-            device_translate_records(d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq, L, d_ref, n_ref, d_aa, d_flags, d_err, stream);
-        },
-        lap, out);
+            device_translate_records(d_nt, d_nt_off, d_nt_len, d_rev, d_aa_off, n_seq, s->L, d_ref, n_ref, d_aa, d_flags, d_err, stream);
+        });
+    lap("reference + K5 + copies");
+    s->chunks.push_back(std::move(c));
+    s->advance(uint32_t(s->chunks.size() - 1), err);
+    lap("row stream");
 }
 
-void filter_captured(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, const RowCapture& cap,
-                     const RecArena& arena, uint32_t L, FilterResult& out) {
-    Laps lap;
-    std::vector<uint64_t> ref_keys;
-    filter_begin(device, reference_binary, reference_keys, L, out, ref_keys, lap);
-    // every sequence must lie inside what it names: K5 reads [off, off + len) of a record's half, or [at, at + len) of the side buffer
-    const size_t n_seq = cap.rows.size() * 2;
-    if (cap.seq.size() != n_seq) throw Error("internal error: captured rows and sequences disagree");
-    for (const RowSeq& rs : cap.seq) {
-        const bool ok = (rs.flags & SRC_MERGE) ? (rs.at <= cap.side.size() && rs.len <= cap.side.size() - rs.at)
-                                               : (rs.len == 0 || (rs.at < arena.n_slots && uint64_t(rs.off) + rs.len <= arena.seq_cap));
-        if (!ok) throw Error("internal error: captured sequence outside the record arena");
-    }
-    if (n_seq && !arena.recs) throw Error("internal error: no device record arena");
-    PodVec<uint64_t> aa_off(n_seq + 1);
-    aa_off[0] = 0;
-    lap("captured rows checked");
-    const RowSeq* d_seq = nullptr;
-    const uint8_t* d_side = nullptr;
-    filter_rows(reference_keys, ref_keys, L, cap.rows, aa_off,
-        [&](hipStream_t stream, std::vector<void*>& owned) -> const uint64_t* {
-            d_seq = to_device(cap.seq, stream, owned);
-            d_side = to_device(cap.side, stream, owned);
-            uint64_t* d_aa_off = nullptr;
-            HIP_OK(hipMalloc(&d_aa_off, (n_seq + 1) * 8)); owned.push_back(d_aa_off);
-            device_row_codon_offsets(d_seq, n_seq, d_aa_off, stream);
-            HIP_OK(hipMemcpyAsync(aa_off.data(), d_aa_off, (n_seq + 1) * 8, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
-            return d_aa_off;
-        },
-        [&](hipStream_t stream, const uint64_t* d_aa_off, const uint64_t* d_ref, uint64_t n_ref, uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err) {
-            device_translate_row_sources(d_seq, n_seq, arena.recs, arena.rec_stride, arena.seq_cap, d_side, d_aa_off, L, d_ref, n_ref, d_aa, d_flags,
-                                         d_err, stream);
-        },
-        lap, out);
+void FilterStream::finish(int device, FilterResult& out) { s->finish(device, out); }
+
+void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
+                   uint32_t L, FilterResult& out) {
+    FilterStream stream(reference_binary, reference_keys, L);
+    stream.add_text(device, tsv_text);
+    stream.finish(device, out);
 }
 
 }  // namespace mp

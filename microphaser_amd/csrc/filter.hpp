@@ -93,16 +93,38 @@ struct FilterResult {
     float translate_ms = 0, stats_ms = 0;
 };
 
-// reference_binary: bytes of the bincode HashSet<Vec<u8>> written by build_reference - or, with reference_keys != nullptr, the
-// peptidome as sorted distinct keys of peptide_len residues, key_words(peptide_len) words each (PeptideResult::keys; reference_binary is then not read);
-// tsv_text: info.tsv of `somatic`. Both buffers are read in place and must stay valid for the call.
+// The filter of a row stream that arrives in parts, in TSV (GTF) order: every add translates its rows on the device (K5) and advances
+// the reference's row stream over them (stop-gain suppression, de-duplication, per-variant-region groups), whose state carries over from
+// one add to the next; finish scores the groups (K6) and writes the five streams. Adds may run on different devices; each part's rows,
+// amino acids and whatever their views point into are owned by the stream until finish. The result is byte for byte that of ONE add of
+// all the rows - and an add that throws reports what that one add would have thrown first.
+// reference_binary: bytes of the bincode HashSet<Vec<u8>> written by build_reference (decoded here, once; a decoding error is reported
+// where the one-part filter reports it: by the first add or by finish) - or, with reference_keys != nullptr, the peptidome as sorted
+// distinct keys of peptide_len residues, key_words(peptide_len) words each (PeptideResult::keys, not copied: it must outlive the stream).
+// The reference goes to each device the stream meets once.
+class FilterStream {
+public:
+    FilterStream(std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, uint32_t peptide_len);
+    ~FilterStream();
+    FilterStream(const FilterStream&) = delete;
+    FilterStream& operator=(const FilterStream&) = delete;
+    // Rows captured from a `somatic` batch that is resident on `device`: the windows are read from its record arena and from cap.side
+    // (k5_translate_row_sources) - no TSV text, no parse, no upload of the windows. `hold` keeps alive what else the rows' views point
+    // into (the downloaded records, a batch's copies of split genes); the data set's gene model must outlive the stream.
+    void add_captured(int device, RowCapture&& cap, const RecArena& arena, std::shared_ptr<const void> hold);
+    // The rows of an info.tsv text (header first), read in place: the text must stay valid until finish.
+    void add_text(int device, std::string_view tsv_text);
+    void finish(int device, FilterResult& out);
+private:
+    struct State;
+    std::unique_ptr<State> s;
+};
+
+// reference_binary / reference_keys as for FilterStream; tsv_text: info.tsv of `somatic`. Both buffers are read in place and must stay
+// valid for the call.
+// (one FilterStream::add_text, then finish). Rows captured from `somatic` batches take the same stream through add_captured: same bytes,
+// counts and errors as filter_device on the TSV those rows would have been written as.
 void filter_device(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, std::string_view tsv_text,
                    uint32_t peptide_len, FilterResult& out);
-
-// The same on rows captured from a `somatic` batch that is still resident on `device`: the windows are read from its record arena and
-// from cap.side (k5_translate_row_sources) - no TSV text, no parse, no upload of the windows. Same bytes, counts and errors as
-// filter_device on the TSV those rows would have been written as. The views of cap.rows must stay valid for the call.
-void filter_captured(int device, std::string_view reference_binary, const std::vector<uint64_t>* reference_keys, const RowCapture& cap,
-                     const RecArena& arena, uint32_t peptide_len, FilterResult& out);
 
 }  // namespace mp

@@ -16,7 +16,7 @@ void device_translate_records(const uint8_t* d_nt, const uint64_t* d_nt_off, con
                               const uint64_t* d_aa_off, uint64_t n_seq, uint32_t L, const uint64_t* d_ref_keys, uint64_t n_ref,
                               uint8_t* d_aa, uint8_t* d_flags, uint32_t* d_err, hipStream_t stream);
 
-// K5 over the rows captured from a resident `somatic` batch (filter_captured), in two steps. First d_aa_off (n_seq + 1 words) gets the
+// K5 over the rows captured from a resident `somatic` batch (FilterStream::add_captured), in two steps. First d_aa_off (n_seq + 1 words) gets the
 // exclusive scan of the sequences' codon counts, the last word their total (the caller reads it to size aa / flags). Then the same
 // per sequence as device_translate_records, the bases read where they lie: record slot i's sequence at d_recs + i * rec_stride + 32,
 // its germline half seq_cap bytes further on; a SRC_MERGE sequence at d_side + at.

@@ -1142,7 +1142,7 @@ void build_batch(const GeneInput* const* genes, size_t n_genes, const ReadStore&
         }
     }
     build_batch_plain(list.data(), list.size(), rs, window_len, normal, b);
-    b.split_inputs = std::move(copies);   // (a deque: the addresses the GeneHosts hold stay valid)
+    b.split_inputs = std::make_shared<const std::deque<GeneInput>>(std::move(copies));   // (a deque: the GeneHosts' addresses stay valid)
     for (size_t p = 0; p < list.size(); p++) {
         if (extra_of[p] == 0xFFFFFFFFu) { b.genes[p].is_extra = true; continue; }
         b.genes[p].n_extra = extra_of[p];

@@ -65,18 +65,15 @@ def cost_ranges(costs, n_chunks):
     return [(bounds[i], bounds[i + 1]) for i in range(len(bounds) - 1) if bounds[i + 1] > bounds[i]]
 
 
-def phase_chunked(ds, n_chunks=4, device=0, window_len=27, contexts=None):
-    """`somatic` on ONE GPU in gene chunks whose legs overlap: while chunk i is phased, downloaded and consumed (host threads + the
-    download DMA), chunk i + 1 is planned, packed and uploaded on a second context of the same GPU (host threads + the upload DMA) -
-    the transfers and the GPU pass of one chunk hide behind the host work of the other (VERDICT r2 item 4: chunked, overlapped
-    transfers). Genes are independent (src/microphasing.rs:895-942), so the chunks' streams concatenate into the single-batch
-    output (TSV header once: shard.merge_streams). Returns (list of Results in gene order, windows); the caller reads or merges
-    the streams (the Results copy their text out of the library only when asked)."""
+def _overlapped_chunks(ds, ranges, window_len, contexts, device, consume):
+    """The overlapped two-context schedule of phase_chunked: a planner thread creates (plans, packs, uploads) the batch of each gene
+    range [lo, hi) on the contexts in turn, while this thread runs consume(batch) on the batch before it - in range order. A context
+    holds one batch at a time: the planner waits until its previous batch has been consumed. Errors of either thread are raised here:
+    the error of the earliest range (what a pass over the ranges one by one would have met first)."""
     import ctypes
     import queue
     import threading
     from . import Batch, Context, lib
-    ranges = cost_ranges(ds.gene_costs(), n_chunks)
     own = contexts is None
     ctxs = [Context(device), Context(device)] if own else list(contexts)
     free = [threading.Semaphore(1) for _ in ctxs]
@@ -84,6 +81,7 @@ def phase_chunked(ds, n_chunks=4, device=0, window_len=27, contexts=None):
     errors = []
 
     def producer():
+        i = 0
         try:
             for i, (lo, hi) in enumerate(ranges):
                 c = i % len(ctxs)
@@ -92,28 +90,24 @@ def phase_chunked(ds, n_chunks=4, device=0, window_len=27, contexts=None):
                     break
                 h = ctypes.c_void_p()
                 ctxs[c]._check(lib().mp_batch_create(ctxs[c]._h, ds._h, MODE_SOMATIC, window_len, lo, hi, ctypes.byref(h)))
-                ready.put((c, Batch(ctxs[c], h, ds)))
+                ready.put((i, c, Batch(ctxs[c], h, ds)))
         except Exception as e:   # noqa: BLE001 - handed to the caller's thread
-            errors.append(e)
+            errors.append((i, e))
         finally:
             ready.put(None)
 
     t = threading.Thread(target=producer, name="mp-chunk-planner")
     t.start()
-    results, windows = [], 0
     try:
         while True:
             item = ready.get()
             if item is None:
                 break
-            c, b = item
+            i, c, b = item
             try:
-                b.run()
-                r = b.results()
-                results.append(r)
-                windows += r.windows
+                consume(b)
             except Exception as e:   # noqa: BLE001
-                errors.append(e)
+                errors.append((i, e))
             finally:
                 b.close()
                 free[c].release()
@@ -125,5 +119,57 @@ def phase_chunked(ds, n_chunks=4, device=0, window_len=27, contexts=None):
             for c in ctxs:
                 c.close()
     if errors:
-        raise errors[0]
-    return results, windows
+        raise min(errors, key=lambda ie: ie[0])[1]
+
+
+def phase_chunked(ds, n_chunks=4, device=0, window_len=27, contexts=None):
+    """`somatic` on ONE GPU in gene chunks whose legs overlap: while chunk i is phased, downloaded and consumed (host threads + the
+    download DMA), chunk i + 1 is planned, packed and uploaded on a second context of the same GPU (host threads + the upload DMA) -
+    the transfers and the GPU pass of one chunk hide behind the host work of the other (VERDICT r2 item 4: chunked, overlapped
+    transfers). Genes are independent (src/microphasing.rs:895-942), so the chunks' streams concatenate into the single-batch
+    output (TSV header once: shard.merge_streams). Returns (list of Results in gene order, windows); the caller reads or merges
+    the streams (the Results copy their text out of the library only when asked)."""
+    results = []
+
+    def consume(b):
+        b.run()
+        results.append(b.results())
+
+    _overlapped_chunks(ds, cost_ranges(ds.gene_costs(), n_chunks), window_len, contexts, device, consume)
+    return results, sum(r.windows for r in results)
+
+
+def filter_chunked(ds, reference, n_chunks=4, peptide_len=9, contexts=None, streams=0, device=0):
+    """`somatic` -> `filter` in gene chunks on phase_chunked's overlapped schedule: every chunk (windows of 3 * peptide_len nt) is run and
+    added to one FilterStream on its own context, while the next chunk is planned and uploaded on the other. reference: a Peptides
+    handle (its peptide length wins over peptide_len, as in Batch.filter) or bincode bytes. Returns (Filtered - the bytes Batch.filter gives on one batch of all genes, and
+    the list of per-chunk Results of `streams` in gene order, or None when streams == 0)."""
+    from . import Context, FilterStream, Peptides
+    if isinstance(reference, Peptides):
+        peptide_len = reference.peptide_len
+    ctxs = [Context(device), Context(device)] if contexts is None else list(contexts)
+    results = []
+    try:
+        fs = FilterStream(ctxs[0], reference, peptide_len)
+        try:
+            failed = []
+
+            def consume(b):
+                if failed:   # (the stream takes nothing after a failed add: the later chunks are not run)
+                    return
+                try:
+                    b.run()
+                    results.append(fs.add(b, streams))
+                except Exception:
+                    failed.append(True)
+                    raise
+
+            _overlapped_chunks(ds, cost_ranges(ds.gene_costs(), n_chunks), 3 * peptide_len, ctxs, device, consume)
+            filtered = fs.finish(ctxs[0])
+        finally:
+            fs.close()
+    finally:
+        if contexts is None:
+            for c in ctxs:
+                c.close()
+    return filtered, (results if streams else None)

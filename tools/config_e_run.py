@@ -8,18 +8,25 @@ so the exome is walked in gene chunks - exactly what the ranks of a multi-GPU ru
 per chunk normal -> FASTA -> build_reference -> sorted distinct keys; the chunks' key arrays are merged by mp_peptides_union; then
 `somatic` per chunk, shards merged by gene, and one `filter` over the merged TSV.
 
-  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--peptide-len 9] [--fused-peptidome] [--fused-filter] [--out config_e.json]
+  python tools/config_e_run.py [--transcripts 20000] [--chunks 8] [--peptide-len 9] [--fused-peptidome] [--fused-filter [--somatic-chunks N]]
+                                [--out config_e.json]
 
 (--fused-peptidome: per chunk `normal` -> Batch.peptidome, the records translated where they lie in device memory, no nucleotide
 FASTA; normal_s then includes the peptidome, build_reference_s is 0, and wall_s["fused_peptidome_s"] is the peptidome call alone)
 
 (--fused-filter: `somatic` as ONE batch over all genes, then Batch.filter against the peptidome - the rows filtered where their windows
 lie in device memory, no info.tsv; somatic_s then includes the filter, filter_s is 0, and wall_s["fused_filter_s"] is the filter call
-alone. One batch, because gene chunks would split the filter's row stream; so --skip-panics, which phases gene by gene, is refused)
+alone. --skip-panics, which phases gene by gene, is refused: a gene left out would not be what the filter of the exome sees)
+
+(--somatic-chunks N with --fused-filter: the tumor half in N gene chunks on pipeline.filter_chunked's overlapped two-context schedule,
+every chunk added to one filter stream; somatic_s then covers the chunks' runs, adds and the stream's finish; default: one batch)
+
+stats["md5"] holds the md5 of the filter's five streams (fasta, normal_fasta, tsv, removed_tsv, removed_fasta), taken after the timing.
 
 (--peptide-len L: windows of 3L nt in `normal` and `somatic`; 13..25 are the MHC class II lengths, with two-word peptide keys)
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -30,6 +37,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 import microphaser_amd as m
+from microphaser_amd.pipeline import filter_chunked
 from microphaser_amd.shard import merge_by_gene, shard_of
 
 
@@ -66,8 +74,12 @@ def main():
     ap.add_argument("--skip-panics", action="store_true", help="leave out genes the reference would panic on (phased gene by gene)")
     ap.add_argument("--fused-peptidome", action="store_true", help="normal -> peptidome on the device (Batch.peptidome), no nucleotide FASTA")
     ap.add_argument("--fused-filter", action="store_true", help="somatic -> filter on the device (Batch.filter), no info.tsv")
+    ap.add_argument("--somatic-chunks", type=int, default=0,
+                    help="with --fused-filter: the tumor half in this many gene chunks, all added to one filter stream (default: one batch)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.somatic_chunks and not a.fused_filter:
+        ap.error("--somatic-chunks is a --fused-filter option")
     if a.fused_filter and a.skip_panics:
         ap.error("--fused-filter phases all genes as one batch (the filter's row stream runs over all of them); --skip-panics phases gene by gene")
     L = a.peptide_len
@@ -124,7 +136,14 @@ def main():
     peptidome = ctx.peptides_union(key_arrays, L)
     t["peptides_union_s"] = time.perf_counter() - t0
     stats["peptidome_size"] = int(peptidome.keys_np.size)
-    if a.fused_filter:
+    if a.fused_filter and a.somatic_chunks:
+        ctx2 = m.Context(0)   # the second context of the overlapped schedule (created outside the timing, as ctx is)
+        t0 = time.perf_counter()
+        f, _ = filter_chunked(ds, peptidome, n_chunks=a.somatic_chunks, peptide_len=L, contexts=[ctx, ctx2])
+        t["somatic_s"], t["filter_s"] = time.perf_counter() - t0, 0.0
+        ctx2.close()
+        stats["somatic_tsv_rows"] = f.rows
+    elif a.fused_filter:
         t0 = time.perf_counter()
         b = ds.batch(window_len=3 * L)
         b.run()
@@ -153,11 +172,13 @@ def main():
         t0 = time.perf_counter()
         f = ctx.filter(merged["tsv"], peptidome)        # the peptidome handle: its keys go to the GPU as they are
         t["filter_s"] = time.perf_counter() - t0
+    stats["md5"] = {k: hashlib.md5(getattr(f, k)).hexdigest() for k in ("fasta", "normal_fasta", "tsv", "removed_tsv", "removed_fasta")}
     stats.update(filter_rows=f.rows, filter_kept=f.kept, filter_removed=f.removed, filter_groups=f.groups, skipped_genes=skipped)
     t["total_s"] = sum(v for k, v in t.items() if k not in ("generate_s", "fused_peptidome_s", "fused_filter_s"))   # (inside normal_s / somatic_s)
     out = {"config": "E: normal + build_reference -l %d + somatic + filter, %d transcripts, %d gene chunks, one MI355X%s" %
                      (L, a.transcripts, a.chunks, (", fused normal -> peptidome" if a.fused_peptidome else "") +
-                                                        (", fused somatic -> filter" if a.fused_filter else "")),
+                                                        (", fused somatic -> filter" if a.fused_filter else "") +
+                                                        (" over %d streamed gene chunks" % a.somatic_chunks if a.somatic_chunks else "")),
            "wall_s": t, "stats": stats}
     print(json.dumps(out))
     if a.out:
